@@ -13,8 +13,11 @@ process per GPU, torchrun) every rank runs its own 4096-ray batch (weak scaling)
 [dW, db, loss] buffer is all-reduced (SUM) over RCCL, then scaled by the global loss (the reference
 seeds its gradient with the loss, train_nerf.py:477).
 
-The default N=1 line also carries, each timed with its own warmup and barrier/synchronize brackets
-after the headline timing:
+A plain run does only what the headline figure needs: set up, --warmup untimed steps, --steps
+timed steps, the outputs of the last timed step if --dump-outputs DIR is given, and the result
+line. With --full the line also carries the per-kernel HIP-event times and roofline figures (extra
+steps after the timed ones), the last step's exceptional-row counts, and at N=1, each timed with
+its own warmup and barrier/synchronize brackets after the headline timing:
   * config2         configs[1]: 1024 rays x 32 samples, MLP 33->30->30->4 (train_nerf.py:189-203)
   * config5_render  configs[4]: the 800x800 x 128-sample forward-only eval render (bf16 MFMA)
   * cpu_baseline    the loma-order C restatement on one host core, and cpu_baseline_mt on every
@@ -55,6 +58,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline timing also measure what takes runs of its own: per-kernel "
+                         "HIP-event times and roofline figures, exceptional-row counts, and at N=1 the "
+                         "config-2 and config-5 records and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (loss, per-ray "
+                         "colours, gradients, updated parameters; the frame with --render) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--config", default="cfg3")
     ap.add_argument("--rays", type=int, default=None, help="rays per GPU (default: config)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -90,9 +101,9 @@ def parse():
     ap.add_argument("--dw-grid", type=int, default=0,
                     help="dW kernel workgroups per step (lnerf_ctx_set_option OPT_DW_GRID; 0 = default 512)")
     ap.add_argument("--no-render", action="store_true",
-                    help="skip the config-5 render record the default N=1 line carries")
+                    help="skip the config-5 render record the --full N=1 line carries")
     ap.add_argument("--no-cfg2", action="store_true",
-                    help="skip the config-2 record the default N=1 line carries")
+                    help="skip the config-2 record the --full N=1 line carries")
     return ap.parse_args()
 
 
@@ -311,6 +322,24 @@ def timed(step, steps, warmup, dist=None, dev=None):
     return dt, t_host
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """Write {name: device tensor} as outdir/<name>.npy (float32), DUMP_LIMIT_BYTES in all: each
+    array gets an equal share of the limit, and one larger than its share is cut down to a fixed
+    seeded sample of its flattened elements (sorted indices, the same from run to run)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays)) // 4
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().float().cpu().numpy())
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(215).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 class Trainer:
     """One configuration's training step on one rank: the engine's fused (or generic) fwd+bwd,
     the RCCL exchange when distributed, and the on-device Adam update."""
@@ -379,6 +408,16 @@ class Trainer:
             self.adam_t += 1
             self.eng.adam_update(self.params, self.grads[0][:-1], self.adam_m, self.adam_v, self.adam_t,
                                  self.args.lr)
+
+    def outputs(self):
+        """What a caller of step() holds after it: the loss, the per-ray colours, the weight and bias
+        gradients (after the exchange and loss seed when distributed) and, with the optimizer in the
+        step, the updated parameters and Adam moments."""
+        _, d_ws, d_bs, loss = self.grads
+        out = {"loss": loss, "acc_color": self.acc, "d_ws": d_ws, "d_bs": d_bs}
+        if not self.args.no_optimizer:
+            out.update(ws=self.ws, bs=self.bs, adam_m=self.adam_m, adam_v=self.adam_v)
+        return out
 
     def kernel_times(self, reps):
         """Per-kernel HIP-event times (ms, on the step's stream) averaged over `reps` extra steps."""
@@ -457,6 +496,8 @@ def bench_render(args, world, rank, local, dist, steps=None, warmup=None):
 
     dt, _ = timed(step, steps, warmup, dist, dev)
     ms = dt / steps * 1e3
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "frame": frame[0] if frame[0] is not None else acc})
     # the render kernel alone (HIP events on the render's stream)
     kms = []
     for _ in range(3):
@@ -627,17 +668,19 @@ def main():
     dt, t_host = timed(t.step, args.steps, args.warmup, dist, t.dev)
     N, S, shapes = t.N, t.S, t.shapes
     ms = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, t.outputs())   # before any further step overwrites them
     total_rays = t.b["N_total"] if args.strong else world * N
     value = total_rays * S / (ms / 1e3)
     # per-kernel HIP-event times over extra timed steps (same stream, same kernels)
-    kt = {} if args.generic else t.kernel_times(max(3, min(args.steps, 10)))
+    kt = t.kernel_times(max(3, min(args.steps, 10))) if args.full and not args.generic else {}
     fused_flops = scene.fused_kernel_flops(shapes) * N * S
     dw_flops = scene.dw_kernel_flops(shapes) * N * S
     step_flops = scene.step_flops(shapes) * N * S
     last_path = None if args.generic else t.eng.last_path()
     # the last step's exceptional rows (lnerf_ctx_exceptional_rows; after the timed region)
     xrows = None
-    if not args.generic and last_path and last_path.get("planes") == 2:
+    if args.full and not args.generic and last_path and last_path.get("planes") == 2:
         n_x, n_last = t.eng.exceptional_rows(split=True)
         xrows = {"rows": n_x, "of_them_last_samples": n_last, "of": len(shapes) * N * S,
                  "floor_guard_fired": t.eng.guard_fired(),
@@ -723,7 +766,7 @@ def main():
                 out["dw_kernel_hbm"]["peak"] = PEAK_HBM_GBS
                 attach_counters(out["dw_kernel_hbm"], "dw16_kernel<2>", "cfg3", out["lib_sha16"],
                                 work=slab_b * N * S)
-        extras = world == 1 and not variants
+        extras = args.full and world == 1 and not variants
         if extras and not args.no_cfg2:
             out["config2"] = bench_config2(args, local)
         if extras and not args.no_render:
@@ -732,7 +775,7 @@ def main():
             r5 = bench_render(argparse.Namespace(x6=False, render_k16=False, steps=5, warmup=2), 1, 0, local, None)
             out["config5_render"] = {k: r5[k] for k in ("metric", "value", "unit", "ms_per_step", "steps",
                                                          "warmup", "dtype", "config", "roofline")}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             c1, cn = cpu_baseline(args, args.config)
             out["cpu_baseline"] = c1
             out["cpu_baseline_mt"] = cn

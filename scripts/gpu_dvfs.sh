@@ -2,10 +2,10 @@
 # weights, interleaved; a large gap means the kernels run at a power-limited clock.
 set -u
 cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out
+LOGS="${LNERF_LOG_DIR:-logs}"; mkdir -p "$LOGS"
 for r in 1 2; do
 for z in "" "--zero-weights"; do
-  timeout -k 10 120 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-render --no-cfg2 $z > gpurun_out/dvfs.log 2>&1 || { echo "failed $z"; tail -3 gpurun_out/dvfs.log; exit 1; }
-  python -c "import json;d=json.loads([l for l in open('gpurun_out/dvfs.log') if l.startswith('{')][-1]);k=d['kernels_ms'];print('${z:-random}', round(d['ms_per_step'],4), 'k1', round(k['fused'],4), 'k2', round(k['dw'],4))"
+  timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-render --no-cfg2 $z > "$LOGS/dvfs.log" 2>&1 || { echo "failed $z"; tail -3 "$LOGS/dvfs.log"; exit 1; }
+  python -c "import json,sys;d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]);k=d['kernels_ms'];print('${z:-random}', round(d['ms_per_step'],4), 'k1', round(k['fused'],4), 'k2', round(k['dw'],4))" "$LOGS/dvfs.log"
 done
 done

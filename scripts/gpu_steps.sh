@@ -9,6 +9,8 @@ cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 R="$GRAFT_REPO_ROOT"
+# the bench step's log directory (LNERF_LOG_DIR, default logs/ in the repository root)
+LOGS="${LNERF_LOG_DIR:-$R/logs}"; mkdir -p "$LOGS"
 lib_sha() { python3 -c "import hashlib,sys; print(hashlib.sha256(open(sys.argv[1],'rb').read()).hexdigest()[:16])" \
   "${LNERF_LIB:-$R/loma-nerf_amd/lib/libloma_nerf.so}"; }
 for step in "$@"; do
@@ -18,8 +20,8 @@ for step in "$@"; do
         --timeout-method thread > gpurun_out/tests.log 2>&1
       rc=$?; tail -3 gpurun_out/tests.log ;;
     bench)
-      timeout -k 10 400 python bench.py > gpurun_out/bench.log 2>&1
-      rc=$?; tail -1 gpurun_out/bench.log | cut -c1-900 ;;
+      timeout -k 10 400 python bench.py --full > "$LOGS/bench.log" 2>&1
+      rc=$?; tail -1 "$LOGS/bench.log" | cut -c1-900 ;;
     dist)
       timeout -k 10 300 python -u -m pytest tests/test_gpu_dist.py -m gpu -x -v -p no:cacheprovider \
         --timeout 120 --timeout-method thread > gpurun_out/dist.log 2>&1 &&

@@ -3,6 +3,7 @@ declares, binds with the argtypes loma's compiler would set, and fails loudly (n
 when no GPU is present. No compute calls are made on the GPU here."""
 import ast
 import ctypes
+import json
 import os
 import re
 import subprocess
@@ -75,20 +76,13 @@ def _loma_ctypes(annotation):
     return t
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SCRIPTS), reason="reference sources not present")
-@pytest.mark.parametrize("script,funcs", [
-    ("nerf.py", ["nerf_evaluate_and_march", "grad_nerf_evaluate_and_march"]),
-    ("mlp_fit.py", ["mlp_fit", "grad_mlp_fit", "mult_a_b"]),
-])
-def test_compiler_shim_binds_reference_programs_with_loma_argtypes(script, funcs):
-    import compiler
-    src = open(os.path.join(REF_SCRIPTS, script)).read()
-    structs, lib = compiler.compile(src, target="c", output_filename="_code/x")
-    assert structs == {}
+def _loma_signatures(src, funcs):
+    """{function: (argtypes loma's compiler would set, restype)} from the annotations of a loma
+    source (compiler.py:262-276; the gradient's from its primal, reverse_diff.py:515-517)."""
     tree = ast.parse(src)
     defs = {n.name: n for n in tree.body if isinstance(n, ast.FunctionDef)}
+    out = {}
     for f in funcs:
-        fn = getattr(lib, f)
         if f.startswith("grad_"):
             fwd = defs[f[len("grad_"):]]
             expect = []
@@ -96,11 +90,56 @@ def test_compiler_shim_binds_reference_programs_with_loma_argtypes(script, funcs
                 t = _loma_ctypes(a.annotation)
                 expect += [t, t if issubclass(t, ctypes._Pointer) else ctypes.POINTER(t)]
             expect.append(ctypes.c_float)      # _dreturn (reverse_diff.py:515-517)
-            assert fn.restype is None
+            out[f] = (expect, None)
         else:
             expect = [_loma_ctypes(a.annotation) for a in defs[f].args.args]
-            ret = defs[f].returns
-            assert fn.restype == (ctypes.c_float if ret is not None else None)
+            out[f] = (expect, ctypes.c_float if defs[f].returns is not None else None)
+    return out
+
+
+def _ctype_from_name(name):
+    """'LP_LP_c_float' -> POINTER(POINTER(c_float)): the recorded names back as ctypes types."""
+    if name is None:
+        return None
+    if name.startswith("LP_"):
+        return ctypes.POINTER(_ctype_from_name(name[3:]))
+    return {"c_float": ctypes.c_float, "c_int": ctypes.c_int}[name]
+
+
+def _recorded_signatures(funcs):
+    """The same signatures as recorded from the reference's sources in
+    tests/golden/loma_argtypes.json (ctypes type names per argument, and the return type)."""
+    with open(os.path.join(REPO, "tests", "golden", "loma_argtypes.json")) as fh:
+        rec = json.load(fh)
+    return {f: ([_ctype_from_name(n) for n in rec[f]["argtypes"]], _ctype_from_name(rec[f]["restype"]))
+            for f in funcs}
+
+
+@pytest.mark.parametrize("script,funcs", [
+    ("nerf.py", ["nerf_evaluate_and_march", "grad_nerf_evaluate_and_march"]),
+    ("mlp_fit.py", ["mlp_fit", "grad_mlp_fit", "mult_a_b"]),
+])
+def test_compiler_shim_binds_reference_programs_with_loma_argtypes(script, funcs):
+    """With the reference's sources at hand the shim compiles them and the expected argtypes come
+    from their annotations (and must equal the recorded ones); without them the library the shim
+    returns (lnerf.load_library(lnerf.LIB_PATH), compiler.py) is checked against the record."""
+    import compiler
+    recorded = _recorded_signatures(funcs)
+    if os.path.isdir(REF_SCRIPTS):
+        src = open(os.path.join(REF_SCRIPTS, script)).read()
+        structs, lib = compiler.compile(src, target="c", output_filename="_code/x")
+        assert structs == {}
+        expected = _loma_signatures(src, funcs)
+        for f in funcs:
+            assert [t.__name__ for t in expected[f][0]] == [t.__name__ for t in recorded[f][0]], f
+            assert expected[f][1] == recorded[f][1], f
+    else:
+        lib = lnerf.load_library(lnerf.LIB_PATH)
+        expected = recorded
+    for f in funcs:
+        fn = getattr(lib, f)
+        expect, restype = expected[f]
+        assert fn.restype == restype, f
         got = fn.argtypes
         assert len(got) == len(expect), f
         for g, e in zip(got, expect):

@@ -71,6 +71,32 @@ def test_variant_labels():
         assert bench.variant_flags(a) == []
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path, monkeypatch):
+    """Small arrays are written whole; one above its share of the limit becomes the same seeded
+    sample of its elements on every call."""
+    import numpy as np
+    import torch
+    small = torch.arange(12, dtype=torch.float64).reshape(4, 3)
+    big = torch.arange(1000, dtype=torch.float32)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 4 * 100)   # 100 elements per array
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s, b = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float32 and s.shape == (4, 3) and (s == small.numpy()).all()
+    assert b.dtype == np.float32 and b.shape == (100,) and len(set(b.tolist())) == 100
+    assert (b == np.load(tmp_path / "b" / "big.npy")).all()
+    assert s.nbytes + b.nbytes <= bench.DUMP_LIMIT_BYTES
+
+
 BLOCKER = textwrap.dedent("""
     import os, sys, time, datetime
     import torch
