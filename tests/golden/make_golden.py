@@ -57,8 +57,17 @@ def pack(w, out, **extra):
 #   nan        z_r = -100 on sample 3: expf(100) overflows, loma's sigmoid adjoint
 #              (x (1 - x) through 1/(1 + e)^2 e, nerf.py:157-165 under rev_diff) is NaN, like
 #              the reference (train_nerf.py:486-489 guards for exactly this)
+#   band       sigma = (1 + U(0,1)) 4e-10 on every sample, the row as small as in `tiny`: every rgb
+#              adjoint sits 2^30 .. 2^36 below its row's sigma adjoint (~sigma / 4, last and other
+#              samples alike) -- inside fp16's subnormals after k1's row shift, above the floor
+#              guard's 2^-37.5 (oracle/edge_band.py; measured 2^31.7 .. 2^35.2)
+#   plain      nothing scaled: rgb pre-activations U(-2, 2), sigma U(0.5, 2); no G element of any
+#              layer more than 2^20 below its row's maximum (measured 2^5.1 at most; the head
+#              rows' smallest element sits at 2^8 after their shift)
 EDGE_FINITE = ("sigma0", "tiny", "denormal", "opaque", "saturated", "sigma_tiny")
 EDGE_NAN = ("sigma0", "nan", "saturated")
+EDGE_BAND = ("band",) * 4
+EDGE_PLAIN = ("plain",) * 4
 
 
 def edge_ray(kind, rng, S=8):
@@ -69,11 +78,18 @@ def edge_ray(kind, rng, S=8):
     sig = {"sigma0": -np.ones(S), "denormal": np.full(S, 24.2), "opaque": np.full(S, 50.0),
            "sigma_tiny": np.full(S, 1e-30), "nan": rng.uniform(0.5, 2, S),
            "saturated": np.where(np.arange(S) % 2 == 0, 0.0, 3.0),
-           "tiny": (np.arange(S) + 1) * 1e-9}[kind]
+           "tiny": (np.arange(S) + 1) * 1e-9}.get(kind)
+    # (the kinds below draw after the table above, which draws the same for every kind: the
+    # committed edge_finite / edge_nan files do not depend on them)
+    if kind == "band":
+        sig = (1.0 + rng.uniform(0, 1, S)) * 4e-10
+    if kind == "plain":
+        sig = rng.uniform(0.5, 2, S)
     x[:, 3] = np.maximum(sig, 0)
     x[:, 7] = np.maximum(-sig, 0)
-    if kind in ("tiny", "sigma_tiny"):   # the whole row as small as sigma (its own exponent group)
-        x[:, [0, 1, 2, 4, 5, 6]] *= 1e-9 if kind == "tiny" else 1e-30
+    # the whole row as small as sigma (its own exponent group)
+    if kind in ("tiny", "sigma_tiny", "band"):
+        x[:, [0, 1, 2, 4, 5, 6]] *= 1e-30 if kind == "sigma_tiny" else 1e-9
     if kind == "saturated":
         x[:, 0:3] = np.where(rng.uniform(size=(S, 3)) < 0.5, 30.0, 0.0)
         x[:, 4:7] = np.where(x[:, 0:3] > 0, 0.0, 30.0)
@@ -82,9 +98,9 @@ def edge_ray(kind, rng, S=8):
     return x
 
 
-def edge_fixture(kinds, S=8):
+def edge_fixture(kinds, S=8, seed=11):
     import oracle
-    rng = np.random.RandomState(11)
+    rng = np.random.RandomState(seed)
     X = np.concatenate([edge_ray(k, rng, S) for k in kinds]).astype(np.float32)
     N = len(kinds)
     I = np.eye(8, dtype=np.float32)
@@ -146,6 +162,17 @@ def main():
     # 5. edge numerics (scripts/nerf.py:157-165,200-232, train_nerf.py:306-311)
     for name, rays in (("edge_finite_6x8.npz", EDGE_FINITE), ("edge_nan_3x8.npz", EDGE_NAN)):
         np.savez_compressed(os.path.join(HERE, name), **edge_fixture(rays))
+    # 6. the fp16x3 band below a G row's maximum, and a benign batch on the same MLP; their
+    # properties are asserted here before the files are written and again by tests/test_oracle.py
+    import edge_band
+    # (seed 17: the first from 11 on whose targets keep every channel's colour residual away from 0;
+    # a residual near 0 puts that channel's adjoints deeper than the band: seed 11 reaches 2^38)
+    g = edge_fixture(EDGE_BAND, seed=17)
+    print("edge_band_4x8:", edge_band.check_band(g))
+    np.savez_compressed(os.path.join(HERE, "edge_band_4x8.npz"), **g)
+    g = edge_fixture(EDGE_PLAIN)
+    print("edge_plain_4x8:", edge_band.check_plain(g))
+    np.savez_compressed(os.path.join(HERE, "edge_plain_4x8.npz"), **g)
     print("fixtures written to", HERE)
 
 

@@ -43,6 +43,27 @@ def test_c_oracle_matches_golden(name, oracle_lib):
     assert_close("d_target", r["d_target"], g["d_target"], **tol)
 
 
+def test_band_fixture_sits_in_the_band():
+    """edge_band_4x8.npz keeps the properties make_golden.py asserted when it wrote it (float64, no
+    GPU): every rgb-descended G element 2^30 .. 2^36 below its row's sigma element -- inside fp16's
+    subnormals after k1's row shift, 1.5 binades above the floor guard's floor --, an emulated fp16x3
+    split of the head row at least 10 bars away from float64 in some dW_1 column (the fixture can
+    fail), and the C oracle's dW, the GPU test's reference, within a tenth of a bar of float64."""
+    import edge_band
+    m = edge_band.check_band(load("edge_band_4x8.npz"))
+    print(m)
+    assert m["head_floor"] > -24   # the guard's floor test (lnerf_internal.h kGuardExp) stays silent
+
+
+def test_plain_fixture_is_benign():
+    """edge_plain_4x8.npz: no G element of any layer more than 2^20 below its row's maximum."""
+    import edge_band
+    m = edge_band.check_plain(load("edge_plain_4x8.npz"))
+    print(m)
+    g, f = load("edge_plain_4x8.npz"), load("edge_finite_6x8.npz")
+    assert np.array_equal(g["wp"], f["wp"]) and np.array_equal(g["bp"], f["bp"])   # shards of one model
+
+
 def test_mult_a_b_known_answer(oracle_lib):
     g = load("mult_a_b.npz")
     c = np.zeros((3, 1), np.float32)
