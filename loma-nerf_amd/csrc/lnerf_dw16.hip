@@ -8,7 +8,10 @@
 //  * global -> registers: a slab tile's half-block is sample-major, [feature half 2][16 samples]
 //    [16 features] (G: fp32, 1 KiB per wave-store of k1; A under fp16x3: int24, 768 B,
 //    lnerf_internal.h a24_slabs), read as fully coalesced 16-B (12-B) loads, 4 features of one
-//    sample per thread, three half-blocks ahead;
+//    sample per thread, over three rotating register sets, each round two half-blocks ahead of its
+//    split;
+//  * a sample's split scales, computed once per workgroup into an LDS table before the loop
+//    (fill_scales), not per half-block in every thread;
 //  * split once, cooperatively: every value is scaled and split into its hi/lo (fp16x3) or
 //    hi/mid/lo (bf16x6) planes exactly once per workgroup and written to a double-buffered LDS
 //    image [plane][16 samples][512 features] (A rows 0..255, G rows 256..511), 8 B per plane and
@@ -30,6 +33,7 @@ namespace lnerf {
 namespace {
 
 typedef float fx4 __attribute__((ext_vector_type(4)));
+typedef float fx3 __attribute__((ext_vector_type(3)));
 typedef float fx16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
@@ -158,7 +162,8 @@ __device__ __forceinline__ int image_row(int i, const RowMap& m) {
 
 struct Loads {
     fx4 v[kRounds];
-    unsigned e;   // the sample's k1 word (sexp_xa, sexp_xg, sexp_dmax)
+    fx3 a24[kRPO];   // int24 A slabs: the three dwords of A round i (v[i] unused: no fourth register)
+    unsigned e;   // the sample's k1 word (sexp_xa, sexp_xg, sexp_dmax): gathered rows only (gather_loads)
 };
 
 // Per-sample balancing of the split: the product of a sample's A row and G row is what dW sums,
@@ -172,64 +177,66 @@ struct Loads {
 // infinity (k1 store_sexp, encoded at shift 0): its G row keeps its own shift and the A row takes
 // the rest of E, so the product scale stays 2^E; its terms are non-finite anyway.
 __device__ __forceinline__ void sample_shifts(unsigned e, int E, int& ea, int& eg) {
+    // selects only: the three cases in one straight line
     const int xa = sexp_xa(e), xg = sexp_xg(e);
-    if (xa == -128 || xg == -128) {
-        ea = xa < -126 ? 0 : xa;
-        eg = xg == -128 ? 0 : xg;
-        return;
-    }
-    if (xa == kSexpNonFinite) {
-        eg = xg;
-        ea = E - xg;
-        return;
-    }
-    const int d = xa + xg - E;   // >= 0
-    ea = xa - (d >> 1);
-    eg = xg - ((d + 1) >> 1);
+    const bool zero = xa == -128 || xg == -128, nonfin = xa == kSexpNonFinite;
+    const int d = xa + xg - E;   // >= 0 for a live row
+    ea = zero ? (xa < -126 ? 0 : xa) : nonfin ? E - xg : xa - (d >> 1);
+    eg = zero ? (xg == -128 ? 0 : xg) : nonfin ? xg : xg - ((d + 1) >> 1);
 }
 
 // Always four loads from valid addresses and no select on the data (nothing waits for it before
 // its use): rows past the layer's tiles are never split, half-blocks past the split land in the
 // idle image and add nothing to db (the callers' hb < hb1 guards).
+// `rounds`: bit i = round i is issued (the rotation issues a half-block's rounds one by one, hb_step3)
+constexpr int kAllRounds = (1 << kRounds) - 1;
 template <bool A24>
-__device__ __forceinline__ void issue_loads(const float* A, const float* G, const unsigned* se, int kt,
-                                            int nt, const RowMap& m, int hb, int hb_end, Loads& L) {
+__device__ __forceinline__ void issue_loads(const float* A, const float* G, int kt, int nt, const RowMap& m,
+                                            int hb, int hb_end, Loads& L, int rounds = kAllRounds) {
     const bool in = hb < hb_end;
     const int hbc = in ? hb : max(0, hb_end - 1);
-    L.e = se[hbc * 16 + m.isamp];
     const int blk = hbc >> 1, half = hbc & 1;
     const float* pg = G + (size_t)blk * nt * 1024 + half * m.hstride;
-    if constexpr (A24) {
+    if (!(rounds & ((1 << kRPO) - 1))) {
+    } else if constexpr (A24) {
         // int24 A slab (k1 store_slab_step24): a tile-block is 3 KiB, its half-blocks 1.5 KiB
-        // [h][n][16 f] x 3 B, so thread u's 4 values are the 12 B at 12 u
-        // (three dword loads the compiler merges into one global_load_dwordx3: a nontemporal load
-        // of a 3-element vector type keeps only its first element)
-        const unsigned char* pa = (const unsigned char*)A + ((size_t)blk * kt * 3072 + half * 1536 + 12 * (threadIdx.x & 127));
+        // [h][n][16 f] x 3 B, so thread u's 4 values are the 12 B at 12 u. Read as buffer loads:
+        // the half-block's base is a wave-uniform descriptor, the tile a scalar offset and the
+        // thread's part a fixed 32-bit offset (as global loads the compiler folds the thread's
+        // offset into a 64-bit per-thread base and adds the uniform part with 64-bit vector adds,
+        // two registers for the whole loop and three adds per load). The descriptor ends with
+        // this half-block's last tile.
+        const unsigned char* pa = (const unsigned char*)A + ((size_t)blk * kt * 3072 + half * 1536);
+        const __amdgpu_buffer_rsrc_t rs =
+            __builtin_amdgcn_make_buffer_rsrc((void*)pa, 0, kt * 3072 - 1536, 0x00020000);
 #pragma unroll
         for (int i = 0; i < kRPO; ++i) {
-            const unsigned* q = (const unsigned*)(pa + m.tile[i] * 3072);
-            L.v[i] = fx4{__builtin_bit_cast(float, __builtin_nontemporal_load(q)),
-                         __builtin_bit_cast(float, __builtin_nontemporal_load(q + 1)),
-                         __builtin_bit_cast(float, __builtin_nontemporal_load(q + 2)), 0.0f};
+            // aux 2: nontemporal, like the G loads
+            // (the whole vector is bit_cast: a bit_cast of one element of it yields element 0 in
+            // this compiler, decode_a24)
+            if (rounds >> i & 1)
+                L.a24[i] = __builtin_bit_cast(fx3, __builtin_amdgcn_raw_buffer_load_b96(rs, 3 * m.lane, m.tile[i] * 3072, 2));
         }
     } else {
         const float* pa = A + (size_t)blk * kt * 1024 + half * m.hstride;
 #pragma unroll
-        for (int i = 0; i < kRPO; ++i) L.v[i] = __builtin_nontemporal_load((const fx4*)(pa + m.tile[i] * 1024 + m.lane));
+        for (int i = 0; i < kRPO; ++i)
+            if (rounds >> i & 1) L.v[i] = __builtin_nontemporal_load((const fx4*)(pa + m.tile[i] * 1024 + m.lane));
     }
 #pragma unroll
-    for (int i = kRPO; i < kRounds; ++i) L.v[i] = __builtin_nontemporal_load((const fx4*)(pg + m.tile[i] * 1024 + m.lane));
+    for (int i = kRPO; i < kRounds; ++i)
+        if (rounds >> i & 1) L.v[i] = __builtin_nontemporal_load((const fx4*)(pg + m.tile[i] * 1024 + m.lane));
 }
 
 // The 4 values of an int24 A round (k1 store_slab_step24): 3 dwords holding the low 24 bits of
 // y_i = 1.5 2^23 + q_i (q_i = rint(x_i 2^(xa + 8)), |q_i| < 2^22, so y_i lies in [2^23, 2^24)
 // where its mantissa field is y_i - 2^23): q_i = float(0x4B000000 | bits) - 1.5 2^23, exact.
-__device__ __forceinline__ fx4 decode_a24(const fx4& raw) {
+__device__ __forceinline__ fx4 decode_a24(const fx3& raw) {
     // bit_cast the whole vector: __builtin_bit_cast of an ext_vector element (raw[1]) yields
     // element 0 in this compiler (ROCm 7.2 clang), which decoded three quarters of A from the
     // wrong dword
-    typedef unsigned ux4 __attribute__((ext_vector_type(4)));
-    const ux4 d = __builtin_bit_cast(ux4, raw);
+    typedef unsigned ux3 __attribute__((ext_vector_type(3)));
+    const ux3 d = __builtin_bit_cast(ux3, raw);
     const unsigned d0 = d[0], d1 = d[1], d2 = d[2];
     const unsigned m0 = d0 & 0xFFFFFFu;
     const unsigned m1 = __builtin_amdgcn_alignbit(d1, d0, 24) & 0xFFFFFFu;
@@ -259,7 +266,14 @@ __device__ __forceinline__ void split4(const fx4& x, bf4& h, bf4& m, bf4& lo) {
 template <int PL>
 __device__ __forceinline__ void write_planes_row(const fx4& v, int i, unsigned char* img, float sa, float sg,
                                                  const RowMap& m) {
-    unsigned char* p = img + m.isamp * kImgRow + 8 * ((image_row(i, m) >> 2) ^ swz(m.isamp));
+    // the round's part of the feature quad (A / G half, tile group) lies above the bits the swizzle
+    // XORs when the groups step by whole multiples of 4 tiles, so it is a constant byte offset from
+    // the thread's one swizzled address (else every round keeps an address register of its own)
+    constexpr bool kRoundConst = kRPO == 1 || kTileGroups % 4 == 0;
+    const int qround = (i < kRPO ? 0 : 64) + 8 * kTileGroups * (i % kRPO);
+    unsigned char* p = kRoundConst
+        ? img + m.isamp * kImgRow + 8 * (((image_row(0, m) >> 2) ^ swz(m.isamp))) + 8 * qround
+        : img + m.isamp * kImgRow + 8 * ((image_row(i, m) >> 2) ^ swz(m.isamp));
     const float sc = i < kRPO ? sa : sg;
     if constexpr (PL == 2) {
         typedef unsigned u2 __attribute__((ext_vector_type(2)));
@@ -313,14 +327,16 @@ __device__ __forceinline__ void sample_scales(unsigned e, int E, float& sa, floa
 
 // round i's values as the split takes them (int24 A rounds decoded). A row k1 marked non-finite
 // (kSexpNonFinite) turns its out-of-range codes (|q| >= 2^22: NaN and +-infinity) back into NaN;
-// the test is one wave-uniform branch, taken only when some lane's sample is marked.
+// `marked`: this thread's sample is such a row; `anym`: some lane's of the wave is (any_marked, tested
+// once per half-block) -- the restore is one wave-uniform branch, taken only then.
+__device__ __forceinline__ bool any_marked(bool marked) { return __builtin_amdgcn_ballot_w64(marked) != 0; }
+
 template <int PL>
-__device__ __forceinline__ fx4 round_values(const Loads& L, int i) {
+__device__ __forceinline__ fx4 round_values(const Loads& L, int i, bool marked, bool anym) {
     if constexpr (a24k(PL)) {
         if (i >= kRPO) return L.v[i];
-        fx4 v = decode_a24(L.v[i]);
-        const bool marked = sexp_xa(L.e) == kSexpNonFinite;
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(marked) != 0, 0)) {
+        fx4 v = decode_a24(L.a24[i]);
+        if (__builtin_expect(anym, 0)) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (marked && __builtin_fabsf(v[j]) >= 4194304.0f) v[j] = __builtin_nanf("");
@@ -334,12 +350,52 @@ __device__ __forceinline__ fx4 round_values(const Loads& L, int i) {
     return L.v[i];
 }
 
-template <int PL>
-__device__ __forceinline__ void write_planes(const Loads& L, unsigned char* img, int E, const RowMap& m) {
+// The per-sample scale table. A sample's scales and its flags depend only on its k1 word and E_l,
+// so the workgroup computes them once per sample (fill_scales, before the half-block loop) into LDS
+// beside the images instead of once per half-block in every thread; in the loop a thread fetches
+// its sample's entry (one ds_read_b64) and nothing branches. An entry is (sa, sg): the final
+// scales of sample_scales (0 for an exceptional row and for the rows past the range's end), with
+// the sign bit of sa set for a row k1 marked non-finite (int24 A slabs; round_values). The table
+// holds one chunk of a split's range (dw_chunk_hb half-blocks and the three past its end the
+// rotation still splits); a longer range runs chunk by chunk.
+struct SampleScale {
     float sa, sg;
-    sample_scales<PL>(L.e, E, sa, sg);
+    bool marked;
+};
+__device__ __forceinline__ SampleScale decode_scale(const float2& t) {
+    const unsigned b = __builtin_bit_cast(unsigned, t.x);
+    return SampleScale{__builtin_bit_cast(float, b & 0x7FFFFFFFu), t.y, (b >> 31) != 0};
+}
+
+// half-blocks past a chunk's end with entries: the rotation splits up to two and fetches a step ahead
+constexpr int kTabPast = 4;
+// Entries of the half-blocks [c0, c1 + kTabPast) of layer words `se`. A half-block past c1 takes the
+// words of half-block c1 - 1, whose values its loads fetch (issue_loads), at scale 0. Returns
+// whether this thread met an exceptional row inside the range (fp16x3: xrow_pass).
+template <int PL>
+__device__ __forceinline__ bool fill_scales(float2* tab, const unsigned* se, int E, int c0, int c1) {
+    bool x = false;
+    const int n = (c1 - c0 + kTabPast) * 16, nin = (c1 - c0) * 16, last = max(0, c1 - 1) * 16;
+    for (int i = threadIdx.x; i < n; i += kThreads) {
+        const bool in = i < nin;
+        const unsigned e = se[in ? c0 * 16 + i : last + (i & 15)];
+        float sa, sg;
+        sample_scales<PL>(e, E, sa, sg);
+        unsigned ba = in ? __builtin_bit_cast(unsigned, sa) : 0u;
+        if constexpr (a24k(PL)) ba |= sexp_xa(e) == kSexpNonFinite ? 0x80000000u : 0u;
+        if constexpr (PL == 2 && LNERF_DW16_XROW) x |= in && xrow(e, E);
+        tab[i] = float2{__builtin_bit_cast(float, ba), in ? sg : 0.0f};
+    }
+    return x;
+}
+
+template <int PL>
+__device__ __forceinline__ void write_planes(const Loads& L, unsigned char* img, const SampleScale& sc,
+                                             const RowMap& m) {
+    const bool anym = a24k(PL) && any_marked(sc.marked);
 #pragma unroll
-    for (int i = 0; i < kRounds; ++i) write_planes_row<PL>(round_values<PL>(L, i), i, img, sa, sg, m);
+    for (int i = 0; i < kRounds; ++i)
+        write_planes_row<PL>(round_values<PL>(L, i, sc.marked, anym), i, img, sc.sa, sc.sg, m);
 }
 
 __device__ __forceinline__ fx16 mfma32(const bf8& a, const bf8& b, fx16 c) {
@@ -374,6 +430,17 @@ __device__ __forceinline__ int frag_off(int f0) {
     return row * kImgRow + 8 * (quad ^ swz(row));
 }
 
+// The fragment t tiles after the one at `base` (this lane's address of an aligned group's first tile,
+// image base + frag_off): a tile is 8 feature quads, and the swizzle only XORs quad bits, so inside a
+// group of 2 or 4 tiles aligned to its size the tile index is an XOR of byte bits 6 and 7. Taken on
+// the final address, it leaves one address register per operand for the whole loop instead of one
+// per tile. (The images start 256-byte aligned.)
+typedef __attribute__((address_space(3))) unsigned char* lds_bytes;
+__device__ __forceinline__ lds_bytes frag_tile(lds_bytes base, int t) {
+    return (lds_bytes)(unsigned long long)((unsigned)(unsigned long long)base ^ (unsigned)(t << 6));
+}
+__device__ __forceinline__ bf8 read_frag(lds_bytes addr) { return read_frag((unsigned char*)addr); }
+
 // One 32 x 32 output tile's products of a half-block: A fragment planes ap, G fragment planes gp
 // (small terms first)
 template <int PL>
@@ -400,7 +467,8 @@ __device__ __forceinline__ fx16 mma_tile(const bf8 (&ap)[nplanes(PL)], const bf8
 // dependent 32x32x16 MFMA pair stalls for the first one's passes; two waves per SIMD hide that with
 // the partner's MFMAs, one wave per SIMD has only its own other tiles). Round-6 default for every
 // wave count: the same sums per accumulator bit for bit; 8 waves measured k2 0.761 ms against
-// 0.765 tile-major (in-process A/B).
+// 0.765 tile-major (in-process A/B). block_mma's read-ahead path (LNERF_DW16_AHEAD) repeats the
+// fp16x3 order below with the plane reads between the products: change both together.
 #ifndef LNERF_DW16_PMAJOR
 #define LNERF_DW16_PMAJOR 1
 #endif
@@ -434,23 +502,51 @@ __device__ __forceinline__ void mma_col(const bf8 (&ap)[TI][nplanes(PL)], const 
 // the split of the next half-block interleaved (round k beside output column tile k), so the
 // VALU split issues under the MFMAs. Branch-free (ACTIVE is a template parameter; past the
 // split's last half-block the zeroed loads land in the idle image buffer).
-template <int PL, int TI, int TJ, bool ACTIVE, bool FULL>
+//
+// Fragment read-ahead (fp16x3, LNERF_DW16_AHEAD): the first things a wave issues after the barrier
+// are this half-block's A fragments and column 0's G planes; `pre` (the db sums, the scale fetch)
+// follows them. Column j + 1's planes are read while column j's MFMAs issue, each in place: its lo
+// plane into the lo buffer as soon as column j's a_hi g_lo products are out (the only ones that
+// use it), its hi plane into the hi buffer once the other products of column j are out; the next
+// column's a_hi g_lo products cover that second read. No register beyond the one column buffer
+// (a second column buffer, or a second hi buffer, made the loop spill). The scheduling barriers keep
+// the reads where the source puts them -- the machine scheduler otherwise sinks each read next to
+// its first consumer, an LDS round trip exposed per plane -- and the compiler still places every
+// wait. The read-ahead path writes mma_col's fp16x3 order out again (a_hi g_lo, a_lo g_hi, a_hi g_hi
+// per accumulator, product-major; it has no tile-major form, so !LNERF_DW16_PMAJOR builds without
+// read-ahead): the two must stay in step.
+#ifndef LNERF_DW16_AHEAD
+#define LNERF_DW16_AHEAD 1
+#endif
+template <int PL, int TI, int TJ, bool ACTIVE, bool FULL, typename Pre, typename Mid>
 __device__ __forceinline__ void block_mma(const unsigned char* img, int a0, int g0, fx16 (&acc)[TI][TJ],
-                                          const Loads& nl, unsigned char* nxt, const RowMap& m, int E,
-                                          bool live = true) {
-    float sa, sg;
-    sample_scales<PL>(nl.e, E, sa, sg);
-    sa = live ? sa : 0.0f;
-    sg = live ? sg : 0.0f;
+                                          const Loads& nl, unsigned char* nxt, const RowMap& m, Pre&& pre,
+                                          Mid&& mid) {
     const unsigned char* fl = img;
     constexpr int NP = nplanes(PL);
+    constexpr bool AHEAD = LNERF_DW16_AHEAD != 0 && LNERF_DW16_PMAJOR != 0 && PL == 2;
     bf8 ap[TI][NP];
+    static_assert((TI & (TI - 1)) == 0 && (TJ & (TJ - 1)) == 0 && TI <= 4 && TJ <= 4, "frag_tile: aligned tile groups");
+    const lds_bytes fa = (lds_bytes)(__attribute__((address_space(3))) void*)(fl + frag_off(a0));
+    const lds_bytes fg = (lds_bytes)(__attribute__((address_space(3))) void*)(fl + frag_off(256 + g0));
+    bf8 glo, ghi;   // AHEAD: the column's lo and hi planes, each re-read in place
+    auto read_g = [&](int j, int p) { return read_frag(frag_tile(fg, j) + p * kPlaneBytes); };
+    SampleScale sc;
+    if constexpr (!AHEAD) sc = pre();
     if constexpr (ACTIVE) {
 #pragma unroll
         for (int i = 0; i < TI; ++i)
 #pragma unroll
-            for (int p = 0; p < NP; ++p) ap[i][p] = read_frag((unsigned char*)fl + p * kPlaneBytes + frag_off(a0 + 32 * i));
+            for (int p = 0; p < NP; ++p) ap[i][p] = read_frag(frag_tile(fa, i) + p * kPlaneBytes);
+        if constexpr (AHEAD) {
+            glo = read_g(0, 1);
+            ghi = read_g(0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
+    if constexpr (AHEAD) sc = pre();
+    const float sa = sc.sa, sg = sc.sg;
+    const bool anym = a24k(PL) && any_marked(sc.marked);
     // RPS split rounds beside each output column tile (8 waves: one; 4 waves: kRounds / TJ)
     constexpr int RPS = (kWavesDw == 8 || TJ >= kRounds) ? 1 : (kRounds + TJ - 1) / TJ;
     constexpr int NR = (kRounds + RPS - 1) / RPS;
@@ -461,7 +557,8 @@ __device__ __forceinline__ void block_mma(const unsigned char* img, int a0, int 
 #pragma unroll
         for (int r = 0; r < RPS; ++r) {
             const int i = k * RPS + r;
-            if (i < kRounds && (FULL || m.ok[i])) write_planes_row<PL>(round_values<PL>(nl, i), i, nxt, sa, sg, m);
+            if (i < kRounds && (FULL || m.ok[i]))
+                write_planes_row<PL>(round_values<PL>(nl, i, sc.marked, anym), i, nxt, sa, sg, m);
         }
     };
 #pragma unroll
@@ -470,51 +567,85 @@ __device__ __forceinline__ void block_mma(const unsigned char* img, int a0, int 
         if constexpr (ACTIVE) {
             if (k < TJ) {
                 const int j = k < TJ ? k : 0;
-                bf8 gp[NP];
+                if constexpr (AHEAD) {
+                    // (a_hi g_lo, a_lo g_hi, a_hi g_hi), product-major as mma_col
 #pragma unroll
-                for (int p = 0; p < NP; ++p) gp[p] = read_frag((unsigned char*)fl + p * kPlaneBytes + frag_off(256 + g0 + 32 * j));
-                mma_col<PL, TI, TJ>(ap, gp, acc, j);
+                    for (int i = 0; i < TI; ++i) acc[i][j] = mfma32h(ap[i][0], glo, acc[i][j]);
+                    if (j + 1 < TJ) {
+                        glo = read_g(j + 1, 1);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+#pragma unroll
+                    for (int i = 0; i < TI; ++i) acc[i][j] = mfma32h(ap[i][1], ghi, acc[i][j]);
+#pragma unroll
+                    for (int i = 0; i < TI; ++i) acc[i][j] = mfma32h(ap[i][0], ghi, acc[i][j]);
+                    if (j + 1 < TJ) {
+                        ghi = read_g(j + 1, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                } else {
+                    bf8 gp[NP];
+#pragma unroll
+                    for (int p = 0; p < NP; ++p) gp[p] = read_g(j, p);
+                    mma_col<PL, TI, TJ>(ap, gp, acc, j);
+                }
             }
         }
         if (LNERF_DW16_SPLIT_LATE) split(k);
+        if (k < NR) mid(((1 << RPS) - 1) << (k * RPS) & kAllRounds);
     }
 }
 
-// Three half-blocks in flight: step I of a 3-step rotation over the load
-// register sets (images alternate at run time). Entering half-block hb: its planes are in image
-// (hb - hb0) & 1, the set after I holds hb + 1 (split now into the other image), the one after
-// that hb + 2 (in flight) and set I is free: it receives hb + 3.
+// round_by_round: a step issues the loads of half-block hb + DEPTH into the free set `fr` one round at
+// a time (`mid`), round i when round i of the set being split (`nx`) has gone into the image. The
+// sets stay apart (fr's registers are its own), but a round of fr now becomes live only when a
+// round of nx dies, so under the 3-deep rotation the sets in flight hold two half-blocks of live
+// registers at any time instead of three, and every load is DEPTH - 1 whole half-blocks ahead of
+// its split. With all of a set's loads at the top of the step the 3-deep loop spilled load
+// destinations, each stored behind a wait for the load just issued.
+//
+// Three register sets of loads: step I of a 3-step rotation over them (images alternate at run
+// time). Entering half-block hb: its planes are in image (hb - hb0) & 1, the set after I holds
+// hb + 1 (split now into the other image), the one after that hb + 2 (in flight) and set I is
+// free: it receives hb + 3, round by round as the rounds of hb + 1 are split (`mid`).
 template <int PL, int TI, int TJ, bool ACTIVE, bool FULL, int I>
-__device__ __forceinline__ void hb_step3(const float* A, const float* G, const unsigned* se, int kt, int nt,
+__device__ __forceinline__ void hb_step3(const float* A, const float* G, const float2* tab, int kt, int nt,
                                          const RowMap& m, int hb, int hb0, int hb1, int a0, int g0,
                                          fx16 (&acc)[TI][TJ], Loads& L0, Loads& L1, Loads& L2, fx4 (&dbs)[kRPO],
-                                         unsigned char* lds, int E, bool& xany) {
+                                         unsigned char* lds, float2& scn) {
     constexpr int kIB = image_bytes<PL>();
     Loads& fr = I == 0 ? L0 : I == 1 ? L1 : L2;
     const Loads& nx = I == 0 ? L1 : I == 1 ? L2 : L0;
-    issue_loads<a24k(PL)>(A, G, se, kt, nt, m, hb + 3, hb1, fr);
-    if (hb + 1 < hb1) {
+    // the db sums and the scales of hb + 1 (`tab`: this thread's sample's
+    // column of the scale table, entry 0 = half-block hb0)
+    auto pre = [&]() {
+        if (hb + 1 < hb1) {
 #pragma unroll
-        for (int i = 0; i < kRPO; ++i) dbs[i] += nx.v[kRPO + i];
-    }
+            for (int i = 0; i < kRPO; ++i) dbs[i] += nx.v[kRPO + i];
+        }
+        // (hb + 1's entry was fetched a step ahead, so nothing here waits for the table; hb + 2's follows)
+        const SampleScale sc = decode_scale(scn);
+        scn = tab[(hb + 2 - hb0) * 16];
+        return sc;
+    };
+    // (round_by_round above)
+    auto mid = [&](int rounds) { issue_loads<a24k(PL)>(A, G, kt, nt, m, hb + LNERF_DW16_DEPTH, hb1, fr, rounds); };
     const int cur = (hb - hb0) & 1;
-    block_mma<PL, TI, TJ, ACTIVE, FULL>(lds + cur * kIB, a0, g0, acc, nx, lds + (cur ^ 1) * kIB, m, E, hb + 1 < hb1);
-    // (after the split of hb + 1, which already waited for its k1 word)
-    if constexpr (PL == 2 && LNERF_DW16_XROW) xany |= hb + 1 < hb1 && xrow(nx.e, E);
+    block_mma<PL, TI, TJ, ACTIVE, FULL>(lds + cur * kIB, a0, g0, acc, nx, lds + (cur ^ 1) * kIB, m, pre, mid);
     __syncthreads();
 }
 
 template <int PL, int TI, int TJ, bool ACTIVE, bool FULL>
-__device__ __forceinline__ void hb_loop3(const float* A, const float* G, const unsigned* se, int kt, int nt,
+__device__ __forceinline__ void hb_loop3(const float* A, const float* G, const float2* tab, int kt, int nt,
                                          const RowMap& m, int hb0, int hb1, int a0, int g0, fx16 (&acc)[TI][TJ],
                                          Loads& L0, Loads& L1, Loads& L2, fx4 (&dbs)[kRPO], unsigned char* lds,
-                                         int E, bool& xany) {
+                                         float2& scn) {
     // whole triples only (one loop body; remainder copies make the compiler spill the
     // accumulators): the steps past hb1 split zero-scaled (zero) planes and add nothing
     for (int hb = hb0; hb < hb1; hb += 3) {
-        hb_step3<PL, TI, TJ, ACTIVE, FULL, 0>(A, G, se, kt, nt, m, hb, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, E, xany);
-        hb_step3<PL, TI, TJ, ACTIVE, FULL, 1>(A, G, se, kt, nt, m, hb + 1, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, E, xany);
-        hb_step3<PL, TI, TJ, ACTIVE, FULL, 2>(A, G, se, kt, nt, m, hb + 2, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, E, xany);
+        hb_step3<PL, TI, TJ, ACTIVE, FULL, 0>(A, G, tab, kt, nt, m, hb, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
+        hb_step3<PL, TI, TJ, ACTIVE, FULL, 1>(A, G, tab, kt, nt, m, hb + 1, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
+        hb_step3<PL, TI, TJ, ACTIVE, FULL, 2>(A, G, tab, kt, nt, m, hb + 2, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
     }
 }
 
@@ -522,33 +653,37 @@ __device__ __forceinline__ void hb_loop3(const float* A, const float* G, const u
 // entering hb, set I held hb (split last step, free: it receives hb + 2), set I ^ 1 holds hb + 1
 // (split now). 17 fewer registers than the 3-deep rotation.
 template <int PL, int TI, int TJ, bool ACTIVE, bool FULL, int I>
-__device__ __forceinline__ void hb_step2(const float* A, const float* G, const unsigned* se, int kt, int nt,
+__device__ __forceinline__ void hb_step2(const float* A, const float* G, const float2* tab, int kt, int nt,
                                          const RowMap& m, int hb, int hb0, int hb1, int a0, int g0,
                                          fx16 (&acc)[TI][TJ], Loads& L0, Loads& L1, fx4 (&dbs)[kRPO],
-                                         unsigned char* lds, int E, bool& xany) {
+                                         unsigned char* lds, float2& scn) {
     constexpr int kIB = image_bytes<PL>();
     Loads& fr = I == 0 ? L0 : L1;
     const Loads& nx = I == 0 ? L1 : L0;
-    issue_loads<a24k(PL)>(A, G, se, kt, nt, m, hb + 2, hb1, fr);
-    if (hb + 1 < hb1) {
+    auto pre = [&]() {
+        if (hb + 1 < hb1) {
 #pragma unroll
-        for (int i = 0; i < kRPO; ++i) dbs[i] += nx.v[kRPO + i];
-    }
+            for (int i = 0; i < kRPO; ++i) dbs[i] += nx.v[kRPO + i];
+        }
+        // (hb + 1's entry was fetched a step ahead, so nothing here waits for the table; hb + 2's follows)
+        const SampleScale sc = decode_scale(scn);
+        scn = tab[(hb + 2 - hb0) * 16];
+        return sc;
+    };
+    // (round_by_round above)
+    auto mid = [&](int rounds) { issue_loads<a24k(PL)>(A, G, kt, nt, m, hb + LNERF_DW16_DEPTH, hb1, fr, rounds); };
     const int cur = (hb - hb0) & 1;
-    block_mma<PL, TI, TJ, ACTIVE, FULL>(lds + cur * kIB, a0, g0, acc, nx, lds + (cur ^ 1) * kIB, m, E, hb + 1 < hb1);
-    // (after the split of hb + 1, which already waited for its k1 word)
-    if constexpr (PL == 2 && LNERF_DW16_XROW) xany |= hb + 1 < hb1 && xrow(nx.e, E);
+    block_mma<PL, TI, TJ, ACTIVE, FULL>(lds + cur * kIB, a0, g0, acc, nx, lds + (cur ^ 1) * kIB, m, pre, mid);
     __syncthreads();
 }
 
 template <int PL, int TI, int TJ, bool ACTIVE, bool FULL>
-__device__ __forceinline__ void hb_loop2(const float* A, const float* G, const unsigned* se, int kt, int nt,
+__device__ __forceinline__ void hb_loop2(const float* A, const float* G, const float2* tab, int kt, int nt,
                                          const RowMap& m, int hb0, int hb1, int a0, int g0, fx16 (&acc)[TI][TJ],
-                                         Loads& L0, Loads& L1, fx4 (&dbs)[kRPO], unsigned char* lds, int E,
-                                         bool& xany) {
+                                         Loads& L0, Loads& L1, fx4 (&dbs)[kRPO], unsigned char* lds, float2& scn) {
     for (int hb = hb0; hb < hb1; hb += 2) {
-        hb_step2<PL, TI, TJ, ACTIVE, FULL, 0>(A, G, se, kt, nt, m, hb, hb0, hb1, a0, g0, acc, L0, L1, dbs, lds, E, xany);
-        hb_step2<PL, TI, TJ, ACTIVE, FULL, 1>(A, G, se, kt, nt, m, hb + 1, hb0, hb1, a0, g0, acc, L0, L1, dbs, lds, E, xany);
+        hb_step2<PL, TI, TJ, ACTIVE, FULL, 0>(A, G, tab, kt, nt, m, hb, hb0, hb1, a0, g0, acc, L0, L1, dbs, lds, scn);
+        hb_step2<PL, TI, TJ, ACTIVE, FULL, 1>(A, G, tab, kt, nt, m, hb + 1, hb0, hb1, a0, g0, acc, L0, L1, dbs, lds, scn);
     }
 }
 
@@ -569,8 +704,8 @@ __device__ __forceinline__ void gather_loads(const float* A, const float* G, con
 #pragma unroll
         for (int i = 0; i < kRPO; ++i) {
             const unsigned* q = (const unsigned*)(pa + m.tile[i] * 3072);
-            L.v[i] = fx4{__builtin_bit_cast(float, q[0]), __builtin_bit_cast(float, q[1]),
-                         __builtin_bit_cast(float, q[2]), 0.0f};
+            L.a24[i] = fx3{__builtin_bit_cast(float, q[0]), __builtin_bit_cast(float, q[1]),
+                           __builtin_bit_cast(float, q[2])};
         }
     } else {
         const float* pa = A + (size_t)blk * kt * 1024 + half * 512 + 4 * u;
@@ -685,9 +820,10 @@ __device__ __forceinline__ int2 xrow_pass(const float* A, const float* G, const 
                 sample_scales<PX>(Lc.e, E, sa, sg);
                 sa = pc < 0 ? 0.0f : sa;
                 sg = pc < 0 ? 0.0f : sg;
+                const bool marked = a24k(PX) && sexp_xa(Lc.e) == kSexpNonFinite, anym = a24k(PX) && any_marked(marked);
 #pragma unroll
                 for (int i = 0; i < kRounds; ++i)
-                    if (m.ok[i]) write_planes_row<PX>(round_values<PX>(Lc, i), i, lds, sa, sg, m);
+                    if (m.ok[i]) write_planes_row<PX>(round_values<PX>(Lc, i, marked, anym), i, lds, sa, sg, m);
                 __syncthreads();
                 if (active) mma_block<PX, TI, TJ>(lds, a0, g0, acc);
                 __syncthreads();
@@ -699,6 +835,25 @@ __device__ __forceinline__ int2 xrow_pass(const float* A, const float* G, const 
     }
     return int2{tail, ntail};
 }
+
+// LDS of a dW workgroup: the two half-block images -- under fp16x3 the exceptional rows' bf16x6
+// image and position ring (xrow_pass) reuse and extend them -- and behind them the scale table
+// (fill_scales) of one chunk of the split's range: as many half-blocks as the workgroup's 160 KiB
+// leave room for, at most 720, a multiple of the rotation's 3 steps (the bench batch's splits are
+// 231 half-blocks: one chunk)
+template <int PL>
+constexpr int dw_image_bytes() {
+    constexpr int main = 2 * image_bytes<PL>();
+    constexpr int xr = PL == 2 && LNERF_DW16_XROW ? image_bytes<kXrowPL>() + (kXrowRing + 9 * kWavesDw) * 4 : 0;
+    return ((main > xr ? main : xr) + 15) / 16 * 16;
+}
+template <int PL>
+constexpr int dw_chunk_hb() {
+    constexpr int room = (160 * 1024 - dw_image_bytes<PL>()) / (16 * (int)sizeof(float2)) - kTabPast;
+    return (room > 720 ? 720 : room) / 6 * 6;
+}
+template <int PL>
+constexpr int dw_lds_bytes() { return dw_image_bytes<PL>() + (dw_chunk_hb<PL>() + kTabPast) * 16 * (int)sizeof(float2); }
 
 // One split of layer l with TI x TJ tile blocks per wave (the layer's ceil(KT/TI) x ceil(NT/TJ)
 // blocks on waves 0.., at most 8).
@@ -732,40 +887,44 @@ __device__ __forceinline__ void dw_split(const Dw16Args& a, int l, int sp, unsig
     const unsigned* se = a.sexp + (size_t)l * a.rpad;
     const int E = a.eshift[l];
     const bool full = KT == 8 && NT == 8;
+    // chunk by chunk (one chunk unless the range outgrows the scale table): the chunk's scales, its
+    // first loads, its first half-block's planes, then the rotation. A chunk is an even number of
+    // half-blocks and whole triples, so a following chunk starts on image 0 right after the last
+    // step's barrier, and only the split's last chunk runs steps past its end (on zero planes).
+    float2* tab = (float2*)(lds + dw_image_bytes<PL>());
+    bool xany = false;   // this thread met an exceptional row of the range (fp16x3: xrow_pass)
+    for (int c0 = hb0; c0 < hb1; c0 += dw_chunk_hb<PL>()) {
+        const int c1 = min(hb1, c0 + dw_chunk_hb<PL>());
+        xany |= fill_scales<PL>(tab, se, E, c0, c1);
+        const float2* tabt = tab + m.isamp;
 #if LNERF_DW16_DEPTH == 2
-    Loads L0, L1;
-    bool xany = false;   // this thread split an exceptional row (fp16x3: xrow_pass)
-    issue_loads<a24k(PL)>(A, G, se, KT, NT, m, hb0, hb1, L0);
-    issue_loads<a24k(PL)>(A, G, se, KT, NT, m, hb0 + 1, hb1, L1);
-    if (hb0 < hb1) {
-#pragma unroll
-        for (int i = 0; i < kRPO; ++i) dbs[i] += L0.v[kRPO + i];
-        write_planes<PL>(L0, lds, E, m);
-        if constexpr (PL == 2 && LNERF_DW16_XROW) xany = xrow(L0.e, E);
-    }
-    __syncthreads();
-    if (active && full) hb_loop2<PL, TI, TJ, true, true>(A, G, se, KT, NT, m, hb0, hb1, a0, g0, acc, L0, L1, dbs, lds, E, xany);
-    else if (active) hb_loop2<PL, TI, TJ, true, false>(A, G, se, KT, NT, m, hb0, hb1, a0, g0, acc, L0, L1, dbs, lds, E, xany);
-    else if (full) hb_loop2<PL, TI, TJ, false, true>(A, G, se, KT, NT, m, hb0, hb1, a0, g0, acc, L0, L1, dbs, lds, E, xany);
-    else hb_loop2<PL, TI, TJ, false, false>(A, G, se, KT, NT, m, hb0, hb1, a0, g0, acc, L0, L1, dbs, lds, E, xany);
+        Loads L0, L1;
+        issue_loads<a24k(PL)>(A, G, KT, NT, m, c0, c1, L0);
+        issue_loads<a24k(PL)>(A, G, KT, NT, m, c0 + 1, c1, L1);
 #else
-    Loads L0, L1, L2;
-    bool xany = false;   // this thread split an exceptional row (fp16x3: xrow_pass)
-    issue_loads<a24k(PL)>(A, G, se, KT, NT, m, hb0, hb1, L0);
-    issue_loads<a24k(PL)>(A, G, se, KT, NT, m, hb0 + 1, hb1, L1);
-    issue_loads<a24k(PL)>(A, G, se, KT, NT, m, hb0 + 2, hb1, L2);
-    if (hb0 < hb1) {
+        Loads L0, L1, L2;
+        issue_loads<a24k(PL)>(A, G, KT, NT, m, c0, c1, L0);
+        issue_loads<a24k(PL)>(A, G, KT, NT, m, c0 + 1, c1, L1);
+        issue_loads<a24k(PL)>(A, G, KT, NT, m, c0 + 2, c1, L2);
+#endif
+        __syncthreads();   // the table is written
 #pragma unroll
         for (int i = 0; i < kRPO; ++i) dbs[i] += L0.v[kRPO + i];
-        write_planes<PL>(L0, lds, E, m);
-        if constexpr (PL == 2 && LNERF_DW16_XROW) xany = xrow(L0.e, E);
-    }
-    __syncthreads();
-    if (active && full) hb_loop3<PL, TI, TJ, true, true>(A, G, se, KT, NT, m, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, E, xany);
-    else if (active) hb_loop3<PL, TI, TJ, true, false>(A, G, se, KT, NT, m, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, E, xany);
-    else if (full) hb_loop3<PL, TI, TJ, false, true>(A, G, se, KT, NT, m, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, E, xany);
-    else hb_loop3<PL, TI, TJ, false, false>(A, G, se, KT, NT, m, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, E, xany);
+        write_planes<PL>(L0, lds, decode_scale(tabt[0]), m);
+        float2 scn = tabt[16];   // the scales of c0 + 1, a step ahead (hb_step3)
+        __syncthreads();
+#if LNERF_DW16_DEPTH == 2
+        if (active && full) hb_loop2<PL, TI, TJ, true, true>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, dbs, lds, scn);
+        else if (active) hb_loop2<PL, TI, TJ, true, false>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, dbs, lds, scn);
+        else if (full) hb_loop2<PL, TI, TJ, false, true>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, dbs, lds, scn);
+        else hb_loop2<PL, TI, TJ, false, false>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, dbs, lds, scn);
+#else
+        if (active && full) hb_loop3<PL, TI, TJ, true, true>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
+        else if (active) hb_loop3<PL, TI, TJ, true, false>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
+        else if (full) hb_loop3<PL, TI, TJ, false, true>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
+        else hb_loop3<PL, TI, TJ, false, false>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
 #endif
+    }
 
     if constexpr (PL == 2 && LNERF_DW16_XROW) {
         const int2 nx = xrow_pass<TI, TJ>(A, G, se, KT, NT, m, hb0, hb1, a0, g0, active, acc, lds, E, xany);
@@ -836,19 +995,10 @@ __host__ __device__ __forceinline__ int dw_shape(int kt, int nt) {
     return 5;
 }
 
-// LDS of a dW workgroup: the two half-block images; under fp16x3 the exceptional rows' bf16x6 image
-// and position ring (xrow_pass) reuse and extend them
-template <int PL>
-constexpr int dw_lds_bytes() {
-    constexpr int main = 2 * image_bytes<PL>();
-    constexpr int xr = PL == 2 && LNERF_DW16_XROW ? image_bytes<kXrowPL>() + (kXrowRing + 9 * kWavesDw) * 4 : 0;
-    return main > xr ? main : xr;
-}
-
 template <int PL>
 __global__ void __launch_bounds__(kThreads, 1) __attribute__((amdgpu_waves_per_eu(kWavesDw / 4, kWavesDw / 4)))
 dw16_kernel(Dw16Args a) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[dw_lds_bytes<PL>()];
+    __shared__ __attribute__((aligned(256))) unsigned char lds[dw_lds_bytes<PL>()];
     if (a.gate && *a.gate == 0) return;
     int li = 0;
     while (li + 1 < a.nl && (int)blockIdx.x >= a.wg_off[li + 1]) ++li;
@@ -924,7 +1074,7 @@ __global__ void __launch_bounds__(1024) k1_reduce_kernel(const int* __restrict__
 
 // compile-time settings of this object that differ from the product build (lnerf_build_knobs)
 unsigned dw16_build_knobs() {
-    return (LNERF_DW16_SPLIT_LATE != 1 ? kKnobDwSplitLate : 0u) | (LNERF_DW16_DEPTH != 3 ? kKnobDwDepth : 0u) |
+    return (LNERF_DW16_SPLIT_LATE != 1 ? kKnobDwSplitLate : 0u) | (LNERF_DW16_AHEAD != 1 ? kKnobDwAhead : 0u) | (LNERF_DW16_DEPTH != 3 ? kKnobDwDepth : 0u) |
            (LNERF_DW16_SWZ != 1 ? kKnobDwSwz : 0u) | (LNERF_A24 != 1 ? kKnobA24 : 0u) |
            (LNERF_DW16_XROW != 1 ? kKnobDwXrow : 0u) |
            (LNERF_DW16_WAVES != 8 || !LNERF_DW16_PMAJOR ? kKnobDwWaves : 0u);

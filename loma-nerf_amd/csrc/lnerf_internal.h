@@ -101,6 +101,7 @@ enum : unsigned {
     kKnobK16Only = 1u << 8, kKnobDwSplitLate = 1u << 9, kKnobDwDepth = 1u << 10, kKnobDwSwz = 1u << 11,
     kKnobK16Pin = 1u << 12, kKnobK16FdSrc = 1u << 13, kKnobKrStagger = 1u << 15, kKnobDwXrow = 1u << 17,
     kKnobGuard = 1u << 25, kKnobK16G2 = 1u << 26, kKnobKrSched = 1u << 18, kKnobDwWaves = 1u << 14, kKnobKrDist = 1u << 19, kKnobPeDoubling = 1u << 20, kKnobK16OneChunk = 1u << 22, kKnobK16WaveComp = 1u << 23, kKnobK16EpiFma = 1u << 24,
+    kKnobDwAhead = 1u << 27,
 };
 unsigned k16_build_knobs();
 unsigned dw16_build_knobs();
