@@ -171,6 +171,24 @@ enum {
     LNERF_RENDER_K16 = 16384, /* lnerf_render in plain bf16: k16's forward (one 16-sample group
                                  per wave) instead of kr (lnerf_render.hip: two groups per wave,
                                  each weight fragment read from LDS feeds both; A/B)           */
+    LNERF_WANT_DINPUT = 32768, /* also produce d_x as the gradient with respect to the batch's own x,
+                                 in x's layout: ENCODED (rays*S, k[0]), the same code path as
+                                 LNERF_WANT_DX and bit-identical to it; POINTS (rays*S, 3), the
+                                 reverse of positional_encoding_3d (pos_encoding.py:38-69); RAYS
+                                 (rays, 6) = [d_o, d_d], also the reverse of o + d t
+                                 (train_nerf.py:289-299; the depths and dists depend only on
+                                 near_t, far_t and S, so there is no dists term). On the fused
+                                 path (every precision, LNERF_K16_W4) and the generic one. d_x is
+                                 overwritten (also under LNERF_ACCUMULATE) and carries the seed
+                                 like the other per-ray adjoints (the loss under
+                                 LNERF_SEED_LOSS); a NULL d_x computes nothing. Together with
+                                 LNERF_WANT_DX on non-ENCODED input: an error. lnerf_render
+                                 ignores it. The encoded gradient goes through a scratch buffer
+                                 the context owns (not part of lnerf_workspace_bytes); its
+                                 reverse (lnerf_input_grad's kernel) runs last in the step, so
+                                 lnerf_ctx_timings counts it in [4] and [5]. At most 39
+                                 frequencies. An extension (no loma counterpart: the reference
+                                 encodes in numpy and never differentiates it).                */
     LNERF_ONE_WAVE = 1024     /* removed in round 4 (the one-wave-per-SIMD kernel pair): an error.
                                  At most one LNERF_MFMA_* precision flag may be set; any fused-
                                  path flag (LNERF_MFMA_*, LNERF_K16_W4) on a shape the fused path
@@ -190,7 +208,8 @@ typedef struct {
     float* acc_color;    /* (rays, 3)                                   */
     float* d_ws;         /* (L, w_k, w_n) padded                        */
     float* d_bs;         /* (L, w_n)                                    */
-    float* d_x;          /* (rays*S, k[0]) with LNERF_WANT_DX           */
+    float* d_x;          /* (rays*S, k[0]) with LNERF_WANT_DX; in x's   */
+                         /* own layout with LNERF_WANT_DINPUT           */
     float* d_dists;      /* (rays, S)                                   */
     float* d_target;     /* (rays, 3)                                   */
 } lnerf_outputs;
@@ -221,13 +240,38 @@ int lnerf_train_step(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* ws, cons
  * LNERF_INPUT_RAYS. K (3x3) and c2w (3x4 or the top of a 4x4, row-major) are host arrays. */
 int lnerf_get_rays(int width, const double* K, const double* c2w, float* rays, void* stream);
 
+/* The reverse of the engine's input producers applied to a caller-supplied d_encoded
+ * (rays*S, 3 + 6F): the kernel LNERF_WANT_DINPUT runs. POINTS: d_input (rays*S, 3), per coordinate c
+ * d_p[c] = dE[c] + sum_f 2^f (cos(2^f p_c) dE[3+6f+c] - sin(2^f p_c) dE[6+6f+c]), the reverse of
+ * positional_encoding_3d (pos_encoding.py:38-69). RAYS: d_input (rays, 6) = [sum_j d_p[j],
+ * sum_j t_j d_p[j]] with t = linspace(near_t, far_t, S), also the reverse of o + d t
+ * (train_nerf.py:289-299). float64 arithmetic on the forward's own points and sin / cos values,
+ * one rounding to float32; fixed-order sums (repeated calls give the same bits). `batch` supplies
+ * x, rays, samples (no upper limit), input_mode (POINTS or RAYS only), num_freqs (0..39) and
+ * near_t / far_t; target and dists are ignored and may be NULL. `scale` (nullable) is a device
+ * scalar multiplied in. An extension (no loma counterpart). */
+int lnerf_input_grad(const lnerf_batch* batch, const float* d_encoded, const float* scale,
+                     float* d_input, void* stream);
+
+/* The reverse of lnerf_get_rays (train_nerf.py:23-62) with respect to c2w: d_c2w (12 device
+ * doubles, 3x4 row-major) from d_rays (n, 6) device floats = [d_o, d_d]:
+ * d_c2w[a][3] = sum_p d_o[p][a], d_c2w[a][b] = sum_p d_d[p][a] dir_b(p) for b < 3, dir(p) the
+ * float64 camera-frame direction lnerf_get_rays forms for the pixel of ray p. `pixels` is a device
+ * array of n int32 indices into the width x width grid (repeats allowed); NULL means
+ * n == width*width and ray p belongs to pixel p. An index outside the grid is skipped by the kernel
+ * (it contributes nothing; nothing is read out of bounds and no error is reported). K (3x3) is a
+ * host array. Two fixed-order float64 stages (deterministic). An extension (no loma counterpart). */
+int lnerf_pose_grad(int width, const double* K, const int* pixels, int n, const float* d_rays,
+                    double* d_c2w, void* stream);
+
 /* Forward only (eval render, train_nerf.py:616-661): acc_color and, if target != NULL, loss. */
 int lnerf_render(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* ws, const float* bs,
                  const lnerf_batch* batch, int flags, const lnerf_outputs* out, void* stream);
 
 /* Per-kernel times (ms) of the last LNERF_TIMING step or render on `ctx`, measured with HIP events
  * on its stream: [0] weight pack, [1] fused fwd+reverse-chain kernel (a render: the forward
- * kernel), [2] loss reduce, [3] dW kernel, [4] dW/db reduce, [5] whole step (0 for the kernels a
+ * kernel), [2] loss reduce, [3] dW kernel, [4] dW/db reduce (with LNERF_WANT_DINPUT also the
+ * input-gradient kernel), [5] whole step (0 for the kernels a
  * render does not run). Synchronises on the step. Returns the number
  * of values written (0 if no timed step ran on the fused path). */
 int lnerf_ctx_timings(lnerf_ctx* ctx, float* ms_out, int n);

@@ -464,6 +464,7 @@ struct lnerf_ctx {
     hipStream_t stream = nullptr;
     DevBuf fused_ws;
     DevBuf generic_ws;
+    DevBuf dinput_ws;    // LNERF_WANT_DINPUT: the encoded gradient (R, k[0]) the input-gradient kernel reads
     std::mutex mu;
     hipEvent_t ev[7] = {};
     bool timed = false;
@@ -694,7 +695,18 @@ extern "C" int lnerf_train_step(lnerf_ctx* ctx, const lnerf_mlp* mlp, const floa
         validate_head(mlp, batch, flags);
         if (!ws || !bs) fail("null weights");
         lnerf_outputs o = out ? *out : lnerf_outputs{};
-        if (!(flags & LNERF_WANT_DX)) o.d_x = nullptr;
+        // LNERF_WANT_DINPUT: d_x in x's own layout. ENCODED input: that is LNERF_WANT_DX, on its code
+        // path. POINTS / RAYS: the step writes the encoded gradient to the context's scratch and the
+        // input-gradient kernel reverses it into the caller's d_x.
+        if (flags & LNERF_WANT_DINPUT) {
+            if (batch->input_mode == LNERF_INPUT_ENCODED) flags |= LNERF_WANT_DX;
+            else if (flags & LNERF_WANT_DX)
+                fail("LNERF_WANT_DX | LNERF_WANT_DINPUT needs ENCODED input (d_x cannot hold both layouts)");
+            else if (batch->num_freqs > kMaxInputGradFreqs)
+                fail("LNERF_WANT_DINPUT runs at most %d frequencies", kMaxInputGradFreqs);
+        }
+        if (!(flags & (LNERF_WANT_DX | LNERF_WANT_DINPUT))) o.d_x = nullptr;
+        float* d_input = (flags & LNERF_WANT_DX) ? nullptr : o.d_x;   // non-null: reverse the encoding
         if (flags & LNERF_HEAD_FIT) o.d_dists = nullptr;
         check_precision_flags(flags);
         std::lock_guard<std::mutex> lock(ctx->mu);
@@ -703,7 +715,10 @@ extern "C" int lnerf_train_step(lnerf_ctx* ctx, const lnerf_mlp* mlp, const floa
         ctx->last_k16_train = false;
         HIP_OK(hipSetDevice(ctx->device));
         hipStream_t s = (hipStream_t)stream;   // NULL: the device's default (null) stream
-        if (use_fused(*mlp, *batch, flags)) {
+        const bool fused = use_fused(*mlp, *batch, flags);
+        if (d_input)
+            o.d_x = (float*)ctx->dinput_ws.get((size_t)batch->rays * batch->samples * mlp->k[0] * sizeof(float));
+        if (fused) {
             const size_t bytes = fused_workspace_bytes(*mlp, batch->rays, batch->samples, true, ctx->dw_grid);
             FusedPlan p{};
             void* wsb = ctx->fused_ws.get(bytes);
@@ -725,7 +740,8 @@ extern "C" int lnerf_train_step(lnerf_ctx* ctx, const lnerf_mlp* mlp, const floa
                 p.w16x = nullptr;
             }
             const bool timed = (flags & LNERF_TIMING) != 0;
-            fused_train_step(p, ws, bs, *batch, seed, flags, o, s, timed ? ctx->ev : nullptr, guarded ? &px : nullptr);
+            fused_train_step(p, ws, bs, *batch, seed, flags, o, s, timed ? ctx->ev : nullptr, guarded ? &px : nullptr,
+                             d_input);
             check_launch("lnerf_train_step");
             ctx->timed = timed;
             ctx->last_path = path_bits(p, true);
@@ -733,6 +749,8 @@ extern "C" int lnerf_train_step(lnerf_ctx* ctx, const lnerf_mlp* mlp, const floa
             ctx->last_k16_train = true;
         } else {
             generic_step(ctx, *mlp, ws, bs, *batch, seed, flags, o, true, s);
+            // (the generic reverse pass has seeded the encoded gradient already)
+            if (d_input) k_input_grad(*batch, o.d_x, nullptr, d_input, s);
             ctx->timed = false;
             ctx->last_path = LNERF_PATH_GENERIC;
         }
@@ -746,6 +764,49 @@ extern "C" int lnerf_get_rays(int width, const double* K, const double* c2w, flo
         if (width < 1 || !K || !c2w || !rays) fail("lnerf_get_rays: bad arguments");
         k_get_rays(width, K, c2w, rays, (hipStream_t)stream);
         check_launch("lnerf_get_rays");
+    });
+}
+
+// The entry points below take no context: they need a device all the same (no CPU path).
+static void need_device() {
+    int n = 0;
+    HIP_OK(hipGetDeviceCount(&n));
+    if (n < 1) fail("no HIP device visible");
+}
+
+extern "C" int lnerf_input_grad(const lnerf_batch* batch, const float* d_encoded, const float* scale,
+                                float* d_input, void* stream) {
+    return guard_int([&]() {
+        // (validate() serves the steps and insists on a target; this call has none)
+        if (!batch || !batch->x || !d_encoded || !d_input) fail("lnerf_input_grad: null argument");
+        if (batch->input_mode != LNERF_INPUT_POINTS && batch->input_mode != LNERF_INPUT_RAYS)
+            fail("lnerf_input_grad: input_mode must be LNERF_INPUT_POINTS or LNERF_INPUT_RAYS");
+        if (batch->num_freqs < 0 || batch->num_freqs > kMaxInputGradFreqs)
+            fail("lnerf_input_grad: num_freqs %d outside 0..%d", batch->num_freqs, kMaxInputGradFreqs);
+        if (batch->rays < 1 || batch->samples < 1) fail("lnerf_input_grad: empty batch");
+        if ((long long)batch->rays * batch->samples > (long long)std::numeric_limits<int>::max())
+            fail("lnerf_input_grad: more than 2^31 - 1 sample rows");
+        need_device();
+        k_input_grad(*batch, d_encoded, scale, d_input, (hipStream_t)stream);
+        check_launch("lnerf_input_grad");
+    });
+}
+
+extern "C" int lnerf_pose_grad(int width, const double* K, const int* pixels, int n, const float* d_rays,
+                               double* d_c2w, void* stream) {
+    return guard_int([&]() {
+        if (width < 1 || width > 46340 || !K || !d_rays || !d_c2w) fail("lnerf_pose_grad: bad arguments");
+        if (n < 1) fail("lnerf_pose_grad: no rays");
+        if (!pixels && n != width * width) fail("lnerf_pose_grad: n must be width * width without pixel indices");
+        need_device();
+        // the stage-1 partials: stream-ordered scratch, so calls on several streams never share it
+        hipStream_t s = (hipStream_t)stream;
+        double* part = nullptr;
+        HIP_OK(hipMallocAsync((void**)&part, (size_t)pose_grad_parts(n) * 12 * sizeof(double), s));
+        k_pose_grad(width, K, pixels, n, d_rays, part, d_c2w, s);
+        const hipError_t launched = hipGetLastError();
+        HIP_OK(hipFreeAsync(part, s));
+        if (launched != hipSuccess) fail("lnerf_pose_grad: kernel launch failed: %s", hipGetErrorString(launched));
     });
 }
 

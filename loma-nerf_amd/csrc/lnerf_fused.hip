@@ -379,7 +379,8 @@ static ReduceArgs reduce_args(const FusedPlan& p, const lnerf_outputs& out, int 
 }
 
 void fused_train_step(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b, float seed,
-                      int flags, const lnerf_outputs& out, hipStream_t s, hipEvent_t* ev, const FusedPlan* px) {
+                      int flags, const lnerf_outputs& out, hipStream_t s, hipEvent_t* ev, const FusedPlan* px,
+                      float* d_input) {
     const bool seed_loss = (flags & LNERF_SEED_LOSS) != 0;
     auto mark = [&](int i) {
         if (ev) (void)hipEventRecord(ev[i], s);
@@ -411,8 +412,11 @@ void fused_train_step(const FusedPlan& p, const float* ws, const float* bs, cons
         if (out.d_dists) k_scale_by_scalar(out.d_dists, (size_t)p.R, p.loss_total, s);
         if (out.d_target)
             k_scale_by_scalar(out.d_target, (size_t)p.rays * (p.head_fit ? p.n[p.L - 1] : 3), p.loss_total, s);
-        if (out.d_x) k_scale_by_scalar(out.d_x, (size_t)p.R * p.k[0], p.loss_total, s);
+        if (out.d_x && !d_input) k_scale_by_scalar(out.d_x, (size_t)p.R * p.k[0], p.loss_total, s);
     }
+    // LNERF_WANT_DINPUT (POINTS / RAYS): out.d_x is the scratch k1 -- or the guard's re-run -- left the
+    // encoded gradient in; its reverse through the encoding applies the loss seed itself
+    if (d_input && out.d_x) k_input_grad(b, out.d_x, seed_loss ? p.loss_total : nullptr, d_input, s);
     mark(5);
 }
 

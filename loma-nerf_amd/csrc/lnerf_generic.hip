@@ -380,12 +380,8 @@ struct RayCam {
 __global__ void get_rays_kernel(int width, RayCam cam, float* rays) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= width * width) return;
-    const int row = p / width, col = p - row * width;
-    // np.linspace(0, 1, width): k * step, the last exactly 1
-    const double step = width > 1 ? 1.0 / (double)(width - 1) : 0.0;
-    const double i = (col == width - 1 && width > 1) ? 1.0 : (double)col * step;
-    const double j = (row == width - 1 && width > 1) ? 1.0 : (double)row * step;
-    const double dir[3] = {(i - cam.K[2]) / cam.K[0], -(j - cam.K[5]) / cam.K[4], -1.0};
+    double dir[3];
+    cam_pixel_dir(width, cam.K, p, dir);
     float* r = rays + (size_t)p * 6;
     for (int a = 0; a < 3; ++a) {
         r[a] = (float)cam.c2w[a * 4 + 3];

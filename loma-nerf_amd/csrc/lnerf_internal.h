@@ -125,6 +125,20 @@ __host__ __device__ inline double ray_point(const float* ray6, int c, int j, int
     return (double)ray6[c] + (double)ray6[3 + c] * ray_depth(j, S, near_t, far_t);
 }
 
+// ---- get_rays (train_nerf.py:23-62), float64 as numpy computes it ------------------------------
+// The camera-frame direction of pixel p of the width x width grid of np.linspace(0, 1, width)
+// (k * step, the last exactly 1): [(i - K[0][2]) / K[0][0], -(j - K[1][2]) / K[1][1], -1]. Shared by
+// get_rays_kernel (lnerf_generic.hip) and its reverse, pose_part_kernel (lnerf_input_grad.hip).
+__host__ __device__ inline void cam_pixel_dir(int width, const double* K, int p, double dir[3]) {
+    const int row = p / width, col = p - row * width;
+    const double step = width > 1 ? 1.0 / (double)(width - 1) : 0.0;
+    const double i = (col == width - 1 && width > 1) ? 1.0 : (double)col * step;
+    const double j = (row == width - 1 && width > 1) ? 1.0 : (double)row * step;
+    dir[0] = (i - K[2]) / K[0];
+    dir[1] = -(j - K[5]) / K[4];
+    dir[2] = -1.0;
+}
+
 // ----------------------------------------------------------------------------------------------
 // Generic ("loma-order") path: one loma call on flat device rectangles. Field meaning follows
 // scripts/nerf.py:1-22; loop bounds are exactly the reference's.
@@ -189,6 +203,18 @@ void k_positional_encoding(const float* pts, int n, int F, float* out, int out_c
                            hipStream_t s);
 void k_adam(float* params, const float* grads, float* m, float* v, size_t n, int t, float lr,
             float beta1, float beta2, float eps, hipStream_t s);
+// Input gradients (lnerf_input_grad.hip). kMaxInputGradFreqs: the most frequencies whose 64 staged
+// rows of 3 + 6F floats fit the kernel's LDS budget.
+constexpr int kMaxInputGradFreqs = 39;
+// d_input = the reverse of the encoding (and, RAYS, of o + d t) applied to dE (rays*S, 3 + 6F),
+// times *scale (nullable): (rays*S, 3) in POINTS mode, (rays, 6) in RAYS mode. b supplies x, rays,
+// samples, input_mode, num_freqs, near_t, far_t.
+void k_input_grad(const lnerf_batch& b, const float* dE, const float* scale, float* d_input, hipStream_t s);
+// the reverse of k_get_rays: d_c2w (12 device doubles) from d_rays (n, 6); `part` is device scratch of
+// pose_grad_parts(n) * 12 doubles
+int pose_grad_parts(int n);
+void k_pose_grad(int width, const double* K, const int* pixels, int n, const float* d_rays, double* part,
+                 double* d_c2w, hipStream_t s);
 
 // ----------------------------------------------------------------------------------------------
 // Fused MFMA path (the throughput path). See DESIGN.md "Kernels".
@@ -279,9 +305,12 @@ void fused_plan(FusedPlan& p, const lnerf_mlp& mlp, const lnerf_batch& b, void* 
 // ev: nullable array of 7 events recorded between the step's kernels (LNERF_TIMING)
 // px (nullable): the bf16x6 plan of the same batch on the same workspace, run gated on p.guard (the
 // fp16x3 floor guard, kGuardExp)
+// d_input (nullable; LNERF_WANT_DINPUT with POINTS / RAYS input): out.d_x is then the context's
+// scratch for the encoded gradient, and d_input receives its reverse through the encoding
+// (k_input_grad), seed applied, after the gated re-run
 void fused_train_step(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b,
                       float seed, int flags, const lnerf_outputs& out, hipStream_t s,
-                      hipEvent_t* ev, const FusedPlan* px = nullptr);
+                      hipEvent_t* ev, const FusedPlan* px = nullptr, float* d_input = nullptr);
 // ev: nullable array of events as fused_train_step's ([1]-[2] bracket the forward kernel)
 void fused_render(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b,
                   const lnerf_outputs& out, hipStream_t s, int flags, hipEvent_t* ev);

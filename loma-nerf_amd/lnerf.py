@@ -37,6 +37,7 @@ K32 = 2048         # removed in round 4 (k32 lost to k16): an error
 K16_W4 = 4096      # fused path: k16 on 4-wave 64-sample workgroups, two per CU (A/B)
 HEAD_FIT = 8192    # the mlp_fit head (sigmoid on every output, no compositing; samples = 1)
 RENDER_K16 = 16384  # render (plain bf16) on k16's forward instead of kr (A/B)
+WANT_DINPUT = 32768  # d_x = the gradient with respect to the batch's own x, in x's layout
 
 OPT_DW_GRID = 1    # lnerf_ctx_set_option: dW workgroups per step (0 = default 512)
 
@@ -47,7 +48,7 @@ EXPORTED_SYMBOLS = [
     "lnerf_workspace_bytes", "lnerf_train_step", "lnerf_render", "lnerf_scale_by_device_scalar",
     "lnerf_adam_update", "lnerf_ctx_timings", "lnerf_get_rays", "lnerf_ctx_last_path",
     "lnerf_ctx_set_option", "lnerf_ctx_relu_masks", "lnerf_build_knobs", "lnerf_ctx_exceptional_rows",
-    "lnerf_ctx_guard_fired",
+    "lnerf_ctx_guard_fired", "lnerf_input_grad", "lnerf_pose_grad",
 ]
 
 # lnerf_ctx_last_path bits
@@ -173,6 +174,13 @@ def configure(lib: ctypes.CDLL) -> None:
         lib.lnerf_ctx_guard_fired.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
     lib.lnerf_get_rays.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                    ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_void_p]
+    if hasattr(lib, "lnerf_input_grad"):   # (older in-tree A/B builds lack the input gradients)
+        lib.lnerf_input_grad.argtypes = [ctypes.POINTER(LnerfBatch), ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p]
+        lib.lnerf_input_grad.restype = ctypes.c_int
+        lib.lnerf_pose_grad.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
+                                        ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        lib.lnerf_pose_grad.restype = ctypes.c_int
     for name in ("lnerf_ctx_timings", "lnerf_ctx_last_path", "lnerf_ctx_set_option", "lnerf_ctx_relu_masks",
                  "lnerf_ctx_exceptional_rows", "lnerf_ctx_guard_fired",
                  "lnerf_ctx_create", "lnerf_train_step", "lnerf_render",
@@ -213,6 +221,7 @@ class StepResult:
     d_dists: object = None
     d_target: object = None
     d_x: object = None
+    d_input: object = None   # want_dinput: the gradient with respect to x, in x's shape
 
 
 class Engine:
@@ -256,10 +265,12 @@ class Engine:
     def train_step(self, mlp: LnerfMLP, ws, bs, x, dists, target, *, samples: int,
                    input_mode: int = INPUT_POINTS, num_freqs: int = 5, seed=None, flags: int = 0,
                    grads=None, want_per_ray: bool = False, want_dx: bool = False,
-                   acc_color=None, near: float = 2.0, far: float = 6.0) -> StepResult:
+                   acc_color=None, near: float = 2.0, far: float = 6.0,
+                   want_dinput: bool = False) -> StepResult:
         """One fwd+bwd over the batch. seed=None seeds with the batch loss (train_nerf.py:477);
         a float seeds with that constant. `grads` (from alloc_grads) is reused if given.
-        INPUT_RAYS: x = (rays, 6) [o, d], dists=None, samples at linspace(near, far, S)."""
+        INPUT_RAYS: x = (rays, 6) [o, d], dists=None, samples at linspace(near, far, S).
+        want_dinput: StepResult.d_input = the gradient with respect to x, in x's shape (WANT_DINPUT)."""
         torch = self.torch
         rays = target.shape[0]
         b = self._batch(rays, samples, input_mode, num_freqs, x, dists, target, near, far)
@@ -275,6 +286,12 @@ class Engine:
         if want_dx:
             d_x = torch.zeros(rays * samples, mlp.k[0], dtype=torch.float32, device=target.device)
             flags |= WANT_DX
+        d_input = None
+        if want_dinput:
+            # (both flags at once: the library decides -- an error unless x is ENCODED)
+            d_input = d_x if d_x is not None else torch.zeros_like(x, dtype=torch.float32)
+            d_x = d_input
+            flags |= WANT_DINPUT
         o = LnerfOutputs(loss.data_ptr(), acc_color.data_ptr(), dws.data_ptr(), dbs.data_ptr(),
                          None if d_x is None else d_x.data_ptr(),
                          None if d_dists is None else d_dists.data_ptr(),
@@ -287,7 +304,8 @@ class Engine:
                                        self._stream())
         if rc != 0:
             raise RuntimeError(f"lnerf_train_step: {last_error()}")
-        return StepResult(loss[0], acc_color, g, dws, dbs, d_dists, d_target, d_x)
+        return StepResult(loss[0], acc_color, g, dws, dbs, d_dists, d_target,
+                          d_x if want_dx else None, d_input)
 
     def mlp_fit_step(self, mlp: LnerfMLP, ws, bs, x, target, *, seed=None, flags: int = 0, grads=None,
                      outputs=None, want_grad: bool = True):
@@ -339,6 +357,41 @@ class Engine:
                                      ctypes.c_void_p(out.data_ptr()), self._stream())
         if rc != 0:
             raise RuntimeError(f"lnerf_get_rays: {last_error()}")
+        return out
+
+    def input_grad(self, x, d_encoded, *, samples: int, input_mode: int, num_freqs: int,
+                   near: float = 2.0, far: float = 6.0, scale=None):
+        """lnerf_input_grad: the reverse of the positional encoding (INPUT_POINTS: x (rows, 3) ->
+        (rows, 3)) and of the ray sampling o + d t (INPUT_RAYS: x (rays, 6) -> (rays, 6) = [d_o, d_d])
+        applied to d_encoded (rows, 3 + 6 num_freqs); `scale` is an optional device scalar."""
+        torch = self.torch
+        rays = x.shape[0] if input_mode == INPUT_RAYS else x.shape[0] // samples
+        rows = rays * samples
+        if input_mode == INPUT_POINTS and x.shape[0] != rows:
+            raise ValueError(f"{x.shape[0]} points are not whole rays of {samples} samples")
+        if tuple(d_encoded.shape) != (rows, 3 + 6 * num_freqs):
+            raise ValueError(f"d_encoded is {tuple(d_encoded.shape)}, expected {(rows, 3 + 6 * num_freqs)}")
+        b = LnerfBatch(rays, samples, input_mode, num_freqs, x.data_ptr(), None, None, float(near), float(far))
+        out = torch.empty_like(x, dtype=torch.float32)
+        rc = self.lib.lnerf_input_grad(ctypes.byref(b), _ptr(d_encoded), _ptr(scale), _ptr(out), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_input_grad: {last_error()}")
+        return out
+
+    def pose_grad(self, width: int, K, d_rays, pixels=None):
+        """lnerf_pose_grad, the reverse of get_rays: d_c2w as a float64 (3, 4) device tensor from
+        d_rays (n, 6); `pixels` (optional int32 device tensor, n indices into the width x width grid,
+        repeats allowed) names each ray's pixel, None means ray p is pixel p."""
+        import numpy as np
+        torch = self.torch
+        Kd = np.ascontiguousarray(np.asarray(K, np.float64).reshape(3, 3))
+        if pixels is not None and (pixels.dtype != torch.int32 or pixels.numel() != d_rays.shape[0]):
+            raise ValueError("pixels must be int32, one index per ray")
+        out = torch.empty(3, 4, dtype=torch.float64, device=d_rays.device)
+        rc = self.lib.lnerf_pose_grad(width, Kd.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), _ptr(pixels),
+                                      d_rays.shape[0], _ptr(d_rays), _ptr(out), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_pose_grad: {last_error()}")
         return out
 
     def timings(self):
