@@ -125,7 +125,12 @@ typedef struct {
 enum {
     LNERF_SEED_CONST = 0,     /* gradients seeded with `seed`                                 */
     LNERF_SEED_LOSS = 1,      /* seeded with the batch loss itself (train_nerf.py:477)        */
-    LNERF_ACCUMULATE = 2,     /* add into d_ws/d_bs (loma semantics) instead of overwriting   */
+    LNERF_ACCUMULATE = 2,     /* add into d_ws/d_bs (loma semantics) instead of overwriting:
+                                 one fp32 add per element of the padded layout, so padded
+                                 entries keep their bits (without the flag they are written
+                                 +0). The other outputs are overwritten as always. Fused path
+                                 only: on the generic path (LNERF_GENERIC, or a shape the fused
+                                 path does not take) lnerf_train_step fails and writes nothing */
     LNERF_WANT_DX = 4,        /* also produce d_x (d_layer_input), ENCODED mode only          */
     LNERF_GENERIC = 8,        /* force the stage-by-stage loma-order kernels (no MFMA fusion) */
     LNERF_FAST = 16,          /* require the fused MFMA path (error if the shape is unsupported) */
@@ -202,7 +207,8 @@ enum {
                                  65 536 sample rows up, samples / 128 below, at least 256)       */
 };
 
-/* Optional outputs (device pointers; any may be NULL). */
+/* Optional outputs (device pointers; any may be NULL, and so may the struct's own pointer: a NULL
+ * output is never written). */
 typedef struct {
     float* loss;         /* 1 float                                     */
     float* acc_color;    /* (rays, 3)                                   */
@@ -222,10 +228,22 @@ const char* lnerf_version(void);
    No reference counterpart (engine-only). */
 unsigned lnerf_build_knobs(void);
 
+/* A context owns the device workspace of its steps and renders (grow-only; activation slabs,
+ * partials, packed weights). Every call on a context uses that one workspace, on the stream the
+ * call names, so calls on one context must be ordered on the device: issue them on one stream, or
+ * order the streams yourself (events) so that no two of them overlap, a reallocation for a larger
+ * batch included (it frees the old block). The context's mutex orders only the host side of
+ * concurrent calls. Work on different contexts is independent and may overlap on different
+ * streams. The context creates no stream of its own. */
 int lnerf_ctx_create(lnerf_ctx** out, int device);
 void lnerf_ctx_destroy(lnerf_ctx* ctx);
-/* Bytes of device workspace a train step needs (activation slabs, partials). */
+/* Bytes of device workspace a train step needs (activation slabs, partials) at the default
+ * LNERF_OPT_DW_GRID. */
 size_t lnerf_workspace_bytes(const lnerf_mlp* mlp, int rays, int samples);
+/* Bytes of its workspace the last fused lnerf_train_step / lnerf_render on `ctx` laid out (the
+ * floor guard's re-run included); 0 after a generic-path call. A step whose layout
+ * would pass the bytes allocated for it fails before any launch. For tests. */
+size_t lnerf_ctx_workspace_used(lnerf_ctx* ctx);
 
 /* Forward (PE + MLP + compositing + loss) and reverse pass over the MLP weights: the work of one
  * nerf_evaluate_and_march + grad_nerf_evaluate_and_march pair on the whole batch. */
@@ -264,7 +282,10 @@ int lnerf_input_grad(const lnerf_batch* batch, const float* d_encoded, const flo
 int lnerf_pose_grad(int width, const double* K, const int* pixels, int n, const float* d_rays,
                     double* d_c2w, void* stream);
 
-/* Forward only (eval render, train_nerf.py:616-661): acc_color and, if target != NULL, loss. */
+/* Forward only (eval render, train_nerf.py:616-661, which always has a target image): acc_color
+ * and the loss against batch->target. batch->target is required (NULL: an error, nothing is
+ * launched or written); the loss is always computed and written to out->loss unless that is NULL.
+ * The gradient outputs are ignored. */
 int lnerf_render(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* ws, const float* bs,
                  const lnerf_batch* batch, int flags, const lnerf_outputs* out, void* stream);
 
@@ -295,7 +316,8 @@ int lnerf_ctx_last_path(lnerf_ctx* ctx);
 /* The hidden-layer ReLU decisions of the last training step on `ctx` (k16 path only, for parity
  * tests: scripts/nerf.py:141-144 takes z > 0): `out` (device) receives (L-1) x R x 32 bytes, bit
  * f % 8 of byte [(l R + r) 32 + f / 8] set when feature f of hidden layer l at sample row r was
- * positive. Valid until the next call on `ctx`; an error after any other kind of call. */
+ * positive. Valid until the next call on `ctx`; an error after any other kind of call. A head-only
+ * MLP (L = 1) has no hidden layer: the call succeeds and writes nothing (`out` may be NULL). */
 int lnerf_ctx_relu_masks(lnerf_ctx* ctx, unsigned char* out, size_t out_bytes, void* stream);
 
 /* The exceptional rows of the last training step on `ctx` (k16 + dw16 with the fp16x3 split): the

@@ -461,7 +461,6 @@ extern "C" void mult_a_b(float** a, int a_h, int a_w, float** b, int b_h, int b_
 // =============================================================================================
 struct lnerf_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
     DevBuf fused_ws;
     DevBuf generic_ws;
     DevBuf dinput_ws;    // LNERF_WANT_DINPUT: the encoded gradient (R, k[0]) the input-gradient kernel reads
@@ -472,7 +471,16 @@ struct lnerf_ctx {
     int dw_grid = 0;     // LNERF_OPT_DW_GRID (0: default_dw_grid)
     FusedPlan last_plan{};   // the last fused training step's plan (lnerf_ctx_relu_masks)
     bool last_k16_train = false;
+    size_t ws_used = 0;  // lnerf_ctx_workspace_used
 };
+
+// The plan's carve (fused_plan_tile) against the bytes allocated for it (workspace_floats): the two are
+// written separately, and a plan that ran past the allocation would have its kernels write there.
+static size_t check_workspace(const FusedPlan& p, size_t bytes) {
+    const size_t used = p.ws_floats * sizeof(float);
+    if (used > bytes) fail("internal: the fused plan needs %zu workspace bytes, %zu were allocated", used, bytes);
+    return used;
+}
 
 static int path_bits(const FusedPlan& p, bool train) {
     return LNERF_PATH_FUSED | LNERF_PATH_K16 | (p.tile == 64 ? LNERF_PATH_K16_W4 : 0) |
@@ -512,7 +520,6 @@ extern "C" int lnerf_ctx_create(lnerf_ctx** out, int device) {
         HIP_OK(hipSetDevice(device));
         lnerf_ctx* c = new lnerf_ctx();
         c->device = device;
-        HIP_OK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
         for (auto& e : c->ev) HIP_OK(hipEventCreate(&e));
         *out = c;
     });
@@ -520,7 +527,6 @@ extern "C" int lnerf_ctx_create(lnerf_ctx** out, int device) {
 
 extern "C" void lnerf_ctx_destroy(lnerf_ctx* ctx) {
     if (!ctx) return;
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     for (auto& e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
     delete ctx;
@@ -535,7 +541,8 @@ static void validate(const lnerf_mlp* m, const lnerf_batch* b) {
         if (l > 0 && m->k[l] != m->n[l - 1]) fail("k[%d] != n[%d]", l, l - 1);
     }
     if (b->rays < 1 || b->samples < 1) fail("empty batch");
-    if (!b->x || !b->target) fail("null batch pointer");
+    if (!b->x) fail("null batch pointer: batch->x is required");
+    if (!b->target) fail("null batch pointer: batch->target is required (lnerf_render computes the loss too)");
     if (b->input_mode == LNERF_INPUT_POINTS || b->input_mode == LNERF_INPUT_RAYS) {
         if (b->num_freqs < 0 || m->k[0] != 3 + 6 * b->num_freqs)
             fail("POINTS/RAYS mode needs k[0] == 3 + 6F");
@@ -723,6 +730,7 @@ extern "C" int lnerf_train_step(lnerf_ctx* ctx, const lnerf_mlp* mlp, const floa
             FusedPlan p{};
             void* wsb = ctx->fused_ws.get(bytes);
             fused_plan(p, *mlp, *batch, wsb, flags, true, ctx->dw_grid);
+            ctx->ws_used = 0;
             // the fp16x3 floor guard (lnerf_internal.h kGuardExp) under the default precision: the
             // bf16x6 plan of the same step, run on the device only if k1 finds a hidden G element
             // below fp16x3's floor (an explicit LNERF_MFMA_F16X3 asks for fp16x3 exactly; the mlp_fit
@@ -735,7 +743,10 @@ extern "C" int lnerf_train_step(lnerf_ctx* ctx, const lnerf_mlp* mlp, const floa
                 px.gate = p.guard;
                 px.w16 = p.w16x;   // packed by p's own pack launch, beside its fp16x3 planes
                 px.w16x = nullptr;
+                // (its fp32 activation slabs end the carve later than p's int24 ones)
+                ctx->ws_used = check_workspace(px, bytes);
             } else {
+                ctx->ws_used = check_workspace(p, bytes);
                 p.guard = nullptr;
                 p.w16x = nullptr;
             }
@@ -748,6 +759,7 @@ extern "C" int lnerf_train_step(lnerf_ctx* ctx, const lnerf_mlp* mlp, const floa
             ctx->last_plan = p;
             ctx->last_k16_train = true;
         } else {
+            ctx->ws_used = 0;
             generic_step(ctx, *mlp, ws, bs, *batch, seed, flags, o, true, s);
             // (the generic reverse pass has seeded the encoded gradient already)
             if (d_input) k_input_grad(*batch, o.d_x, nullptr, d_input, s);
@@ -826,7 +838,9 @@ extern "C" int lnerf_render(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* w
         if (use_fused(*mlp, *batch, flags & ~LNERF_WANT_DX)) {
             const size_t bytes = fused_workspace_bytes(*mlp, batch->rays, batch->samples, false, ctx->dw_grid);
             FusedPlan p{};
+            ctx->ws_used = 0;
             fused_plan(p, *mlp, *batch, ctx->fused_ws.get(bytes), flags, false, ctx->dw_grid);
+            ctx->ws_used = check_workspace(p, bytes);
             p.guard = nullptr;   // (the floor guard is a training-step feature)
             p.w16x = nullptr;
             const bool timed = (flags & LNERF_TIMING) != 0;
@@ -835,6 +849,7 @@ extern "C" int lnerf_render(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* w
             ctx->last_path = path_bits(p, false) | (fused_render_uses_kr(p, flags) ? LNERF_PATH_KR : 0);
         } else {
             ctx->timed = false;
+            ctx->ws_used = 0;
             generic_step(ctx, *mlp, ws, bs, *batch, 1.0f, 0, o, false, s);
             ctx->last_path = LNERF_PATH_GENERIC;
         }
@@ -866,13 +881,21 @@ extern "C" int lnerf_ctx_last_path(lnerf_ctx* ctx) {
     return rc != 0 ? rc : path;
 }
 
+extern "C" size_t lnerf_ctx_workspace_used(lnerf_ctx* ctx) {
+    if (!ctx) return 0;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    return ctx->ws_used;
+}
+
 extern "C" int lnerf_ctx_relu_masks(lnerf_ctx* ctx, unsigned char* out, size_t out_bytes, void* stream) {
     return guard_int([&]() {
-        if (!ctx || !out) fail("null argument");
+        if (!ctx) fail("null argument");
         std::lock_guard<std::mutex> lock(ctx->mu);
         if (!ctx->last_k16_train) fail("no k16 training step has run on this context since the last other call");
         const FusedPlan& p = ctx->last_plan;
         const size_t need = (size_t)(p.L - 1) * p.R * 32;
+        if (need == 0) return;   // a head-only MLP has no hidden layer: nothing to write (out may be NULL)
+        if (!out) fail("null argument");
         if (out_bytes < need) fail("relu mask buffer holds %zu bytes, needs %zu", out_bytes, need);
         HIP_OK(hipSetDevice(ctx->device));
         k16_masks_launch(p, out, (hipStream_t)stream);

@@ -337,6 +337,7 @@ static void fused_plan_tile(FusedPlan& p, const lnerf_mlp& m, const lnerf_batch&
     p.xcount = (int*)(base + off);
     if (train) off += align_up((size_t)2 * y.dw_grid, 64);
     p.act = take(y.act_total);
+    p.ws_floats = off;   // the callers hold this against what they allocated (workspace_floats)
 }
 
 void fused_plan(FusedPlan& p, const lnerf_mlp& m, const lnerf_batch& b, void* ws_base, int flags, bool train,

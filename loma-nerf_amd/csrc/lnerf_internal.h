@@ -273,6 +273,7 @@ struct FusedPlan {
     // first; the bf16x6 re-run's kernels (gate = the same word) exit at once unless it is set
     int* guard;                          // nullable: no floor test
     const int* gate;                     // nullable: run unconditionally
+    size_t ws_floats;                    // where the carve ended: the floats of ws_base this plan addresses
 };
 
 // ---- the fp16x3 floor guard (round 6) ----------------------------------------------------------

@@ -48,7 +48,7 @@ EXPORTED_SYMBOLS = [
     "lnerf_workspace_bytes", "lnerf_train_step", "lnerf_render", "lnerf_scale_by_device_scalar",
     "lnerf_adam_update", "lnerf_ctx_timings", "lnerf_get_rays", "lnerf_ctx_last_path",
     "lnerf_ctx_set_option", "lnerf_ctx_relu_masks", "lnerf_build_knobs", "lnerf_ctx_exceptional_rows",
-    "lnerf_ctx_guard_fired", "lnerf_input_grad", "lnerf_pose_grad",
+    "lnerf_ctx_guard_fired", "lnerf_input_grad", "lnerf_pose_grad", "lnerf_ctx_workspace_used",
 ]
 
 # lnerf_ctx_last_path bits
@@ -172,6 +172,9 @@ def configure(lib: ctypes.CDLL) -> None:
                                                    ctypes.POINTER(ctypes.c_longlong)]
     if hasattr(lib, "lnerf_ctx_guard_fired"):   # (round 6; older A/B builds lack it)
         lib.lnerf_ctx_guard_fired.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "lnerf_ctx_workspace_used"):   # (older in-tree A/B builds lack it)
+        lib.lnerf_ctx_workspace_used.argtypes = [ctypes.c_void_p]
+        lib.lnerf_ctx_workspace_used.restype = ctypes.c_size_t
     lib.lnerf_get_rays.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                    ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, ctypes.c_void_p]
     if hasattr(lib, "lnerf_input_grad"):   # (older in-tree A/B builds lack the input gradients)
@@ -419,6 +422,14 @@ class Engine:
         if self.lib.lnerf_ctx_guard_fired(self.ctx, ctypes.byref(f)) != 0:
             raise RuntimeError(f"lnerf_ctx_guard_fired: {last_error()}")
         return int(f.value)
+
+    def workspace_used(self) -> int:
+        """Bytes of the workspace the last fused step / render laid out (lnerf_ctx_workspace_used)."""
+        return int(self.lib.lnerf_ctx_workspace_used(self.ctx))
+
+    def workspace_bytes(self, mlp: LnerfMLP, rays: int, samples: int) -> int:
+        """lnerf_workspace_bytes: what a default-grid training step of this shape needs."""
+        return int(self.lib.lnerf_workspace_bytes(ctypes.byref(mlp), rays, samples))
 
     def last_path(self) -> dict:
         """The kernels the last train_step/render ran (lnerf_ctx_last_path)."""

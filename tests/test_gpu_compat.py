@@ -118,6 +118,69 @@ def test_edge_numerics(lib):
     assert np.array_equal(np.isnan(g["W"]), np.isnan(o["W"]))
 
 
+def test_four_threads_call_the_compat_abi_at_once(lib):
+    """the loma-compat entry points may be called from several threads at once (ctypes
+    drops the GIL); each thread gets its own stream and staging buffers, destroyed when it exits. Four
+    threads run three rounds of nerf_evaluate_and_march + grad_nerf_evaluate_and_march on the chunk
+    workload, thread i against its own target (scaled by 1 + i/8, so a mix-up between the threads'
+    staging shows), each result held to the serial tests' oracle comparison at the serial tests'
+    tolerances. lnerf_last_error() is per thread: one thread's failed call (rejected on the host,
+    nothing launched) is not seen by the others. After the threads are gone the main thread's own
+    context still works."""
+    import threading
+
+    n_threads, rounds = 4, 3
+    w = nerf_np.make_workload("chunk")
+    shapes = [x.shape for x in w.ws]
+    calls = [NerfCall(w.X, w.wp, w.bp, shapes, (w.target * np.float32(1.0 + i / 8.0)).astype(np.float32),
+                      w.dists, w.S) for i in range(n_threads)]
+    # the C oracle, once per variant, on the CPU, before any thread starts
+    want_f = [c.oracle_forward() for c in calls]
+    want_g = [c.oracle_grad(wf["loss"]) for c, wf in zip(calls, want_f)]
+    assert len({float(wf["loss"]) for wf in want_f}) == n_threads   # the variants do differ
+    barrier = threading.Barrier(n_threads, timeout=120)
+    failures, errors = [], {}
+    bad = 2   # the thread that makes the invalid call
+
+    def work(i):
+        try:
+            c = calls[i]
+            barrier.wait()
+            for r in range(rounds):
+                got = c.lib_forward(lib)
+                assert abs(got["loss"] - want_f[i]["loss"]) <= 2e-6 * abs(want_f[i]["loss"]), (i, r)
+                for k in ("io", "rgba", "alpha", "cp", "wsamp", "acc"):
+                    assert_close(f"thread {i} round {r} {k}", got[k], want_f[i][k], **TOL)
+                g = c.lib_grad(lib, want_f[i]["loss"])
+                for k in ("W", "B", "X", "T", "IO", "dists", "acc", "rgba", "alpha", "cp", "wsamp"):
+                    assert_close(f"thread {i} round {r} d{k}", g[k], want_g[i][k], **TOL)
+                assert np.array_equal(g["_io_after"], c.io) and g["_ints"] == [0] * 5
+                assert np.abs(g["W"]).sum() > 0 and not any(g[k].any() for k in ("rgba", "alpha", "cp", "wsamp"))
+            if i == bad:
+                one = to_ctypes(np.zeros((1, 1), np.float32))
+                lib.mult_a_b(one, -1, 1, one, 1, 1, one)   # "negative dimension": fails before any launch
+            barrier.wait()   # every thread's last call has returned; the bad thread's error is set
+            errors[i] = lib.lnerf_last_error().decode()
+            barrier.wait()   # and stays set while the others read theirs
+            if i == bad:
+                assert lib.lnerf_last_error().decode() == errors[i]
+        except BaseException as e:   # noqa: BLE001 - reported by the main thread
+            failures.append((i, e))
+            barrier.abort()
+
+    threads = [threading.Thread(target=work, args=(i,)) for i in range(n_threads)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not failures, failures
+    assert "negative dimension" in errors[bad], errors
+    assert all(errors[i] == "" for i in range(n_threads) if i != bad), errors
+    # the threads' contexts are gone; the main thread's is intact
+    test_chunk_forward_matches_oracle(lib)
+    test_chunk_grad_matches_oracle(lib)
+
+
 @pytest.fixture(scope="module")
 def fitlib(lib):
     return lib
