@@ -289,6 +289,43 @@ int lnerf_pose_grad(int width, const double* K, const int* pixels, int n, const 
 int lnerf_render(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* ws, const float* bs,
                  const lnerf_batch* batch, int flags, const lnerf_outputs* out, void* stream);
 
+/* Render maps: lnerf_render's forward with the standard outputs of a volume renderer beside the
+ * colour, and no need for a target. An extension: the reference computes the per-sample arrays
+ * (img_sample_rgba_arr, weights_samples) but never a depth or an opacity.
+ *   w_j are the reference's own compositing weights, alpha_j T_j with its INCLUSIVE transmittance
+ * (nerf.py:226-272: T_0 = 1, T_j = P_j = prod_{i<=j} (1 - alpha_i + 1e-10) for j >= 1), the
+ * weights acc_color is summed with. So opacity = sum_j w_j stays below 1 even on an opaque ray
+ * (sample j >= 1 is attenuated by its own alpha too), and a ray's last sample (delta = 1e8 in the
+ * reference, alpha = 1 wherever sigma > 0) contributes about 1e-10: the maps are consistent with
+ * the colour the engine returns, not with the textbook exclusive transmittance. depth is not
+ * divided by the opacity. depth, opacity and acc_color are fp32 segmented sums in one order (the
+ * fused kernels' scans; the generic path sums sequentially in j).
+ *   t_j: in RAYS mode (float)linspace(near_t, far_t, S)[j], the depths the engine samples at;
+ * sample_t must be NULL there. In POINTS / ENCODED mode sample_t is a device (rays, S) float array;
+ * asking for depth without it is an error, and nothing else reads it.
+ *   batch->target may be NULL: no loss is computed then, and a non-NULL out->loss is an error.
+ * With a target the loss is lnerf_render's, and acc_color is lnerf_render's bit for bit under the
+ * same flags. Any output pointer may be NULL, and so may `out`: a NULL output is never written. An
+ * error launches nothing and writes nothing. Flags as lnerf_render (the LNERF_MFMA_* precisions,
+ * LNERF_RENDER_K16, LNERF_K16_W4, LNERF_GENERIC, LNERF_FAST, LNERF_TIMING); LNERF_HEAD_FIT is an
+ * error. Shapes the fused path does not take (samples > 128, a head over 16 outputs) run the
+ * generic path, which has no limit on samples. lnerf_ctx_last_path reports the kernels' bits plus
+ * LNERF_PATH_MAPS; the other lnerf_ctx_* queries behave as after lnerf_render. The maps go straight
+ * to the caller's buffers: no workspace beyond lnerf_render's. */
+typedef struct {
+    float* acc_color;  /* (rays, 3)                                                 */
+    float* depth;      /* (rays)      sum_j w_j t_j  (not divided by opacity)       */
+    float* opacity;    /* (rays)      sum_j w_j                                     */
+    float* weights;    /* (rays, S)   w_j = alpha_j T_j, the weights the colour uses */
+    float* rgba;       /* (rays*S, 4) sigmoid(rgb), ReLU(sigma): the reference's
+                          img_sample_rgba_arr; 16-byte aligned                      */
+    float* loss;       /* 1 float; only with batch->target                          */
+} lnerf_render_outputs;
+
+int lnerf_render_maps(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* ws, const float* bs,
+                      const lnerf_batch* batch, const float* sample_t, int flags,
+                      const lnerf_render_outputs* out, void* stream);
+
 /* Per-kernel times (ms) of the last LNERF_TIMING step or render on `ctx`, measured with HIP events
  * on its stream: [0] weight pack, [1] fused fwd+reverse-chain kernel (a render: the forward
  * kernel), [2] loss reduce, [3] dW kernel, [4] dW/db reduce (with LNERF_WANT_DINPUT also the
@@ -309,7 +346,8 @@ enum {
     LNERF_PATH_K32 = 16,      /* reserved (k32, removed in round 4)                           */
     LNERF_PATH_K16_W4 = 32,   /* k16 on 4-wave, 64-sample workgroups (two per CU)             */
     LNERF_PATH_KR = 64,       /* the render ran kr (lnerf_render.hip), not k16's forward      */
-    LNERF_PATH_A24 = 128      /* training kept the activation slabs as int24 (fp16x3)         */
+    LNERF_PATH_A24 = 128,     /* training kept the activation slabs as int24 (fp16x3)         */
+    LNERF_PATH_MAPS = 1024    /* lnerf_render_maps: the MAPS instantiations (bits 8-9: planes)  */
 };
 int lnerf_ctx_last_path(lnerf_ctx* ctx);
 

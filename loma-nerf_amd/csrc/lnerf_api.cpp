@@ -532,7 +532,7 @@ extern "C" void lnerf_ctx_destroy(lnerf_ctx* ctx) {
     delete ctx;
 }
 
-static void validate(const lnerf_mlp* m, const lnerf_batch* b) {
+static void validate(const lnerf_mlp* m, const lnerf_batch* b, bool need_target = true) {
     if (!m || !b) fail("null mlp/batch");
     if (m->num_layers < 1 || m->num_layers > kMaxLayers) fail("num_layers out of range");
     for (int l = 0; l < m->num_layers; ++l) {
@@ -542,7 +542,8 @@ static void validate(const lnerf_mlp* m, const lnerf_batch* b) {
     }
     if (b->rays < 1 || b->samples < 1) fail("empty batch");
     if (!b->x) fail("null batch pointer: batch->x is required");
-    if (!b->target) fail("null batch pointer: batch->target is required (lnerf_render computes the loss too)");
+    if (need_target && !b->target)
+        fail("null batch pointer: batch->target is required (lnerf_render computes the loss too)");
     if (b->input_mode == LNERF_INPUT_POINTS || b->input_mode == LNERF_INPUT_RAYS) {
         if (b->num_freqs < 0 || m->k[0] != 3 + 6 * b->num_freqs)
             fail("POINTS/RAYS mode needs k[0] == 3 + 6F");
@@ -574,7 +575,7 @@ extern "C" size_t lnerf_workspace_bytes(const lnerf_mlp* mlp, int rays, int samp
 // fresh zero arrays for every call, :313-317, :370-392).
 static void generic_step(lnerf_ctx* ctx, const lnerf_mlp& m, const float* ws, const float* bs,
                          const lnerf_batch& bt, float seed, int flags, const lnerf_outputs& out,
-                         bool want_grad, hipStream_t s) {
+                         bool want_grad, hipStream_t s, const comp::MapsArgs* maps = nullptr) {
     const int L = m.num_layers, R = bt.rays * bt.samples, S = bt.samples, th = bt.rays;
     if (want_grad && (flags & LNERF_ACCUMULATE))
         fail("LNERF_ACCUMULATE is only supported on the fused path");
@@ -643,6 +644,13 @@ static void generic_step(lnerf_ctx* ctx, const lnerf_mlp& m, const float* ws, co
     if (out.loss) HIP_OK(hipMemcpyAsync(out.loss, g + oloss, 4, hipMemcpyDeviceToDevice, s));
     if (out.acc_color)
         HIP_OK(hipMemcpyAsync(out.acc_color, g + oacc, (size_t)th * 3 * 4, hipMemcpyDeviceToDevice, s));
+    if (maps) {
+        // lnerf_render_maps: the forward's own img_sample_rgba_arr and weights_samples, and the per-ray
+        // sums of the latter
+        if (maps->rgba) HIP_OK(hipMemcpyAsync(maps->rgba, g + org, nS * 4 * sizeof(float), hipMemcpyDeviceToDevice, s));
+        if (maps->weights) HIP_OK(hipMemcpyAsync(maps->weights, g + ows, nS * sizeof(float), hipMemcpyDeviceToDevice, s));
+        k_ray_maps(g + ows, maps->sample_t, th, S, bt.near_t, bt.far_t, maps->depth, maps->opacity, s);
+    }
     if (!want_grad) return;
     // grad call on fresh zero buffers, seeded with the loss or the constant
     HIP_OK(hipMemsetAsync(g + oIO, 0, (oloss - oIO) * sizeof(float), s));  // primal + adjoints
@@ -854,6 +862,56 @@ extern "C" int lnerf_render(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* w
             ctx->last_path = LNERF_PATH_GENERIC;
         }
         check_launch("lnerf_render");
+    });
+}
+
+extern "C" int lnerf_render_maps(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* ws, const float* bs,
+                                 const lnerf_batch* batch, const float* sample_t, int flags,
+                                 const lnerf_render_outputs* out, void* stream) {
+    return guard_int([&]() {
+        if (!ctx) fail("null ctx");
+        if (flags & LNERF_HEAD_FIT) fail("lnerf_render_maps: LNERF_HEAD_FIT has no compositing to map");
+        validate(mlp, batch, false);
+        validate_head(mlp, batch, flags);
+        if (!ws || !bs) fail("null weights");
+        const lnerf_render_outputs ro = out ? *out : lnerf_render_outputs{};
+        if (!batch->target && ro.loss) fail("lnerf_render_maps: out->loss needs batch->target");
+        if ((uintptr_t)ro.rgba % 16) fail("lnerf_render_maps: out->rgba must be 16-byte aligned (one store per sample)");
+        if (batch->input_mode == LNERF_INPUT_RAYS) {
+            if (sample_t) fail("lnerf_render_maps: sample_t must be NULL in RAYS mode (the engine samples the depths)");
+        } else if (ro.depth && !sample_t) {
+            fail("lnerf_render_maps: depth needs sample_t (rays, S) in POINTS / ENCODED mode");
+        }
+        lnerf_outputs o{};
+        o.loss = ro.loss;
+        o.acc_color = ro.acc_color;
+        comp::MapsArgs maps{ro.depth, ro.opacity, ro.weights, ro.rgba, sample_t};
+        check_precision_flags(flags);
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        ctx->last_k16_train = false;   // a render reuses the workspace the masks live in
+        HIP_OK(hipSetDevice(ctx->device));
+        hipStream_t s = (hipStream_t)stream;   // NULL: the device's default (null) stream
+        const int rflags = flags & ~(LNERF_WANT_DX | LNERF_WANT_DINPUT | LNERF_ACCUMULATE | LNERF_SEED_LOSS);
+        if (use_fused(*mlp, *batch, rflags)) {
+            const size_t bytes = fused_workspace_bytes(*mlp, batch->rays, batch->samples, false, ctx->dw_grid);
+            FusedPlan p{};
+            ctx->ws_used = 0;
+            fused_plan(p, *mlp, *batch, ctx->fused_ws.get(bytes), rflags, false, ctx->dw_grid);
+            ctx->ws_used = check_workspace(p, bytes);
+            p.guard = nullptr;   // (the floor guard is a training-step feature)
+            p.w16x = nullptr;
+            const bool timed = (flags & LNERF_TIMING) != 0;
+            fused_render_maps(p, ws, bs, *batch, o, maps, s, rflags, timed ? ctx->ev : nullptr);
+            ctx->timed = timed;
+            ctx->last_path = path_bits(p, false) | (fused_render_uses_kr(p, rflags) ? LNERF_PATH_KR : 0) |
+                             LNERF_PATH_MAPS;
+        } else {
+            ctx->timed = false;
+            ctx->ws_used = 0;
+            generic_step(ctx, *mlp, ws, bs, *batch, 1.0f, 0, o, false, s, &maps);
+            ctx->last_path = LNERF_PATH_GENERIC | LNERF_PATH_MAPS;
+        }
+        check_launch("lnerf_render_maps");
     });
 }
 

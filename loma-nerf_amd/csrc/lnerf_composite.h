@@ -13,6 +13,23 @@ namespace comp {
 constexpr int kTileSamples = 128;
 constexpr int kCompFloats = 21;            // per-sample compositing scratch floats in LDS (21 TS)
 
+// t_j of sample row gs for the depth map (0 when no depth is wanted)
+template <class A>
+__device__ __forceinline__ float maps_sample_t(const A& a, const MapsArgs& m, size_t gs, int j) {
+    if (!m.depth) return 0.0f;
+    if (a.input_mode == LNERF_INPUT_RAYS) return (float)ray_depth(j, a.S, a.near_t, a.far_t);
+    return m.sample_t[gs];
+}
+// the per-sample maps of one valid sample: one thread per consecutive sample row (coalesced)
+__device__ __forceinline__ void maps_store_sample(const MapsArgs& m, size_t gs, const float (&rgb)[3], float sigma,
+                                                  float wgt) {
+    if (m.weights) m.weights[gs] = wgt;
+    if (m.rgba) {
+        typedef float f4 __attribute__((ext_vector_type(4)));
+        *(f4*)(m.rgba + gs * 4) = f4{rgb[0], rgb[1], rgb[2], sigma};
+    }
+}
+
 // Coordinate c of sample row gs: the given point (POINTS) or o + d t in float64 (RAYS).
 template <class A>
 __device__ __forceinline__ double sample_coord(const A& a, int gs, int c) {
@@ -233,12 +250,18 @@ __device__ __forceinline__ float composite_tile(const A& a, int wg, float* comp,
 // instead of composite_tile's 2 (log2 S + 1). The products and sums associate differently from
 // composite_tile's LDS rounds (and from loma's sequential loops), at fp32 rounding level. Threads
 // 0..TS-1 own one sample each; z [TS][4] at comp[0], the wave partials [TS / 64][4] at comp[4 TS].
-template <int TS, class A>
-__device__ __forceinline__ void composite_fwd_wave(const A& a, int wg, float* comp, float* rayloss) {
+// MAPS (lnerf_render_maps): the scan also carries w and w t (opacity and depth, the colour's order),
+// their wave partials in [TS / 64][2] behind pub's [TS / 64][4]; every valid sample stores its w and
+// rgba; a.target may be NULL (no loss: rayloss 0).
+template <int TS, bool MAPS = false, class A>
+__device__ __forceinline__ void composite_fwd_wave(const A& a, int wg, float* comp, float* rayloss,
+                                                   const MapsArgs& m = MapsArgs{}) {
     static_assert(TS % 64 == 0, "whole waves of samples");
+    static_assert((TS / 64) * 6 <= 4 * TS, "the wave partials fit the idle gz region at 4 TS");
     const int tid = threadIdx.x, S = a.S, lane = tid & 63, wv = tid >> 6;
     float* c_z = comp;
     float* pub = comp + 4 * TS;
+    float* pub2 = pub + (TS / 64) * 4;         // MAPS: the wave partials of w and w t
     const bool act = tid < TS;
     const int ls = act ? tid : 0;
     const int rl = ls / S, j = ls - rl * S;   // ray within the tile, sample within the ray
@@ -247,6 +270,7 @@ __device__ __forceinline__ void composite_fwd_wave(const A& a, int wg, float* co
     const bool valid = act && ls < ntile && ray < a.rays;
     const size_t gs = (size_t)ray * S + j;
     float rgb[3] = {0, 0, 0}, al = 0, cc = 1;
+    float sig = 0, tj = 0;                     // MAPS only
     if (valid) {
         float z[4];
 #pragma unroll
@@ -258,6 +282,10 @@ __device__ __forceinline__ void composite_fwd_wave(const A& a, int wg, float* co
         const float delta = a.dists ? a.dists[gs] : ray_delta(j, S, a.near_t, a.far_t);
         al = 1.0f - expf((0.0f - sigma) * delta);
         cc = (1.0f - al) + (float)(1e-10);
+        if constexpr (MAPS) {
+            sig = sigma;
+            tj = maps_sample_t(a, m, gs, j);
+        }
     }
     const int jw = j < lane ? j : lane;        // this ray's samples before this one in this wave
     const int ws = (ls - j) >> 6;              // the wave holding the ray's first sample
@@ -276,12 +304,28 @@ __device__ __forceinline__ void composite_fwd_wave(const A& a, int wg, float* co
     const float wgt = al * T;
     // colour: the segmented sum of w rgb, read at the ray's last sample
     float cv[3] = {wgt * rgb[0], wgt * rgb[1], wgt * rgb[2]};
+    // MAPS: opacity sum_j w_j and depth sum_j w_j t_j, through the same shuffle rounds
+    float mv[2] = {wgt, wgt * tj};
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float o = __shfl_up(cv[k], d, 64);
             if (jw >= d) cv[k] = o + cv[k];
+        }
+        if constexpr (MAPS) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const float o = __shfl_up(mv[k], d, 64);
+                if (jw >= d) mv[k] = o + mv[k];
+            }
+        }
+    }
+    if constexpr (MAPS) {
+        if (valid) maps_store_sample(m, gs, rgb, sig, wgt);
+        if (act && lane == 63) {
+            pub2[wv * 2] = mv[0];
+            pub2[wv * 2 + 1] = mv[1];
         }
     }
     if (act && lane == 63)
@@ -293,7 +337,24 @@ __device__ __forceinline__ void composite_fwd_wave(const A& a, int wg, float* co
 #pragma unroll
             for (int k = 0; k < 3; ++k) cv[k] = pub[w * 4 + 1 + k] + cv[k];
         float loss = 0.0f;
-        if (valid) {
+        if constexpr (MAPS) {
+            for (int w = wv - 1; w >= ws; --w) {
+                mv[0] = pub2[w * 2] + mv[0];
+                mv[1] = pub2[w * 2 + 1] + mv[1];
+            }
+            if (valid) {
+                if (m.opacity) m.opacity[ray] = mv[0];
+                if (m.depth) m.depth[ray] = mv[1];
+                if (a.target) {
+                    const float* t = a.target + (size_t)ray * 3;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) loss = loss + (cv[k] - t[k]) * (cv[k] - t[k]);
+                }
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    if (a.acc_color) a.acc_color[(size_t)ray * 3 + k] = cv[k];
+            }
+        } else if (valid) {
             const float* t = a.target + (size_t)ray * 3;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -311,8 +372,11 @@ __device__ __forceinline__ void composite_fwd_wave(const A& a, int wg, float* co
 // G_j = a_j + c_{j+1} G_{j+1} by shuffles down plus the later waves' partials: four workgroup
 // barriers instead of composite_tile's 3 log2(S) + 4. LDS: wave partials [TS / 64][8] at 8 TS,
 // c_j at 9 TS, P_j at 10 TS, per-ray dacc [rays][4] at 11 TS (within kCompFloats = 21 per sample).
-template <int TS, class A>
-__device__ __forceinline__ void composite_tile_wave(const A& a, int wg, float* comp, float* rayloss, bool grad) {
+// MAPS (lnerf_render_maps, forward half only: grad must be false): as composite_fwd_wave's, the
+// wave partials of w and w t in pub's free slots 6 and 7.
+template <int TS, bool MAPS = false, class A>
+__device__ __forceinline__ void composite_tile_wave(const A& a, int wg, float* comp, float* rayloss, bool grad,
+                                                    const MapsArgs& m = MapsArgs{}) {
     static_assert(TS % 64 == 0, "whole waves of samples");
     static_assert((TS / 64) * 8 <= TS, "the wave partials [TS / 64][8] fit their TS-float region at 8 TS");
     const int tid = threadIdx.x, S = a.S, lane = tid & 63, wv = tid >> 6;
@@ -341,6 +405,9 @@ __device__ __forceinline__ void composite_tile_wave(const A& a, int wg, float* c
         al = 1.0f - expf((0.0f - sigma) * delta);
         cc = (1.0f - al) + (float)(1e-10);
     }
+    float tj = 0;                              // MAPS only
+    if constexpr (MAPS)
+        if (valid) tj = maps_sample_t(a, m, gs, j);
     const int jw = j < lane ? j : lane;        // this ray's samples before this one in this wave
     const int ws = (ls - j) >> 6;              // the wave holding the ray's first sample
     // P_j, the inclusive product (nerf.py:226-272)
@@ -363,12 +430,28 @@ __device__ __forceinline__ void composite_tile_wave(const A& a, int wg, float* c
     const float wgt = al * T;
     // colour: the segmented sum of w rgb, read at the ray's last sample
     float cv[3] = {wgt * rgb[0], wgt * rgb[1], wgt * rgb[2]};
+    // MAPS: opacity sum_j w_j and depth sum_j w_j t_j, through the same shuffle rounds
+    float mv[2] = {wgt, wgt * tj};
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float o = __shfl_up(cv[k], d, 64);
             if (jw >= d) cv[k] = o + cv[k];
+        }
+        if constexpr (MAPS) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const float o = __shfl_up(mv[k], d, 64);
+                if (jw >= d) mv[k] = o + mv[k];
+            }
+        }
+    }
+    if constexpr (MAPS) {
+        if (valid) maps_store_sample(m, gs, rgb, sigma, wgt);
+        if (act && lane == 63) {
+            pub[wv * 8 + 6] = mv[0];
+            pub[wv * 8 + 7] = mv[1];
         }
     }
     if (act && lane == 63)
@@ -380,7 +463,24 @@ __device__ __forceinline__ void composite_tile_wave(const A& a, int wg, float* c
 #pragma unroll
             for (int k = 0; k < 3; ++k) cv[k] = pub[w * 8 + 1 + k] + cv[k];
         float loss = 0.0f;
-        if (valid) {
+        if constexpr (MAPS) {
+            for (int w = wv - 1; w >= ws; --w) {
+                mv[0] = pub[w * 8 + 6] + mv[0];
+                mv[1] = pub[w * 8 + 7] + mv[1];
+            }
+            if (valid) {
+                if (m.opacity) m.opacity[ray] = mv[0];
+                if (m.depth) m.depth[ray] = mv[1];
+                if (a.target) {
+                    const float* t = a.target + (size_t)ray * 3;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) loss = loss + (cv[k] - t[k]) * (cv[k] - t[k]);
+                }
+#pragma unroll
+                for (int k = 0; k < 3; ++k)
+                    if (a.acc_color) a.acc_color[(size_t)ray * 3 + k] = cv[k];
+            }
+        } else if (valid) {
             const float* t = a.target + (size_t)ray * 3;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -399,7 +499,7 @@ __device__ __forceinline__ void composite_tile_wave(const A& a, int wg, float* c
         }
         rayloss[rl] = loss;
     }
-    if (!grad) return;
+    if (MAPS || !grad) return;
     __syncthreads();
 
     // ---- reverse, per sample ----

@@ -454,4 +454,36 @@ void fused_render(const FusedPlan& p, const float* ws, const float* bs, const ln
     mark(5);
 }
 
+void fused_render_maps(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b,
+                       const lnerf_outputs& out, const comp::MapsArgs& maps, hipStream_t s, int flags,
+                       hipEvent_t* ev) {
+    auto mark = [&](int i) {
+        if (ev) (void)hipEventRecord(ev[i], s);
+    };
+    mark(0);
+    k16_pack(p, ws, bs, s);
+    mark(1);
+    int parts = p.num_wg;
+    if (fused_render_uses_kr(p, flags)) {
+        kr_launch_maps(p, b, out, maps, s);
+        parts = kr_num_wg(p);
+    } else {
+        k16_launch_maps(p, b, out, maps, s);
+    }
+    mark(2);
+    // the loss as fused_render sums it; no target, no loss
+    if (b.target) {
+        if (parts > 4 * 256) {
+            const int per = (parts + kLossStage1 - 1) / kLossStage1;
+            loss_stage1_kernel<<<kLossStage1, 256, 0, s>>>(p.loss_part, parts, per, p.loss_stage);
+            loss_reduce_kernel<<<1, 256, 0, s>>>(p.loss_stage, kLossStage1, p.loss_total, out.loss);
+        } else {
+            loss_reduce_kernel<<<1, 256, 0, s>>>(p.loss_part, parts, p.loss_total, out.loss);
+        }
+    }
+    mark(3);
+    mark(4);
+    mark(5);
+}
+
 }  // namespace lnerf

@@ -444,7 +444,33 @@ void lg_nerf_forward(const LgDims& d, const LgBuffers& b, float* loss_dev, hipSt
     if (d.th > 0)
         lg_composite_fwd_kernel<<<(d.th + 127) / 128, 128, 0, s>>>(
             d, b.IO, b.rgba, b.dists, b.alpha, b.cp, b.wsamp, b.acc, b.cpC, b.cpP);
-    lg_loss_kernel<<<1, 64, 0, s>>>(d, b.acc, d.acc_cols, b.T, loss_dev);
+    // (lnerf_render_maps without a target: no loss stage)
+    if (b.T) lg_loss_kernel<<<1, 64, 0, s>>>(d, b.acc, d.acc_cols, b.T, loss_dev);
+}
+
+// The render maps of the generic path (lnerf_render_maps; an extension): per ray, opacity = sum_j w_j
+// and depth = sum_j w_j t_j over the weights_samples the compositing left, one thread per ray, summed
+// sequentially in j as nerf.py:281-288 sums the colour.
+__global__ void lg_ray_maps_kernel(const float* __restrict__ wsamp, const float* __restrict__ sample_t, int rays,
+                                   int S, float near_t, float far_t, float* depth, float* opacity) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rays) return;
+    const size_t o = (size_t)i * S;
+    float dsum = 0.0f, osum = 0.0f;
+    for (int j = 0; j < S; ++j) {
+        const float w = wsamp[o + j];
+        const float t = sample_t ? sample_t[o + j] : (float)ray_depth(j, S, near_t, far_t);
+        osum = osum + w;
+        dsum = dsum + w * t;
+    }
+    if (opacity) opacity[i] = osum;
+    if (depth) depth[i] = dsum;
+}
+
+void k_ray_maps(const float* wsamp, const float* sample_t, int rays, int S, float near_t, float far_t,
+                float* depth, float* opacity, hipStream_t s) {
+    if (rays > 0 && (depth || opacity))
+        lg_ray_maps_kernel<<<(rays + 127) / 128, 128, 0, s>>>(wsamp, sample_t, rays, S, near_t, far_t, depth, opacity);
 }
 
 void lg_nerf_grad(const LgDims& d, const LgBuffers& b, const LgAdjoints& a, const float* seed_dev,

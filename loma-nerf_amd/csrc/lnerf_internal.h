@@ -331,4 +331,33 @@ bool kr_supported(const FusedPlan& p);
 int kr_num_wg(const FusedPlan& p);
 void kr_launch(const FusedPlan& p, const lnerf_batch& b, const lnerf_outputs& out, hipStream_t s);
 
+// ---- render maps (lnerf_render_maps) -----------------------------------------------------------
+namespace comp {
+// The render maps (lnerf_render_maps; an extension, the reference never forms depth or opacity): what
+// the MAPS variants of composite_fwd_wave / composite_tile_wave write besides acc_color. Every
+// pointer is nullable; a NULL map is never written. sample_t (POINTS / ENCODED input) is read only
+// when depth is wanted; RAYS input takes t_j = (float)ray_depth(j, S, near_t, far_t).
+struct MapsArgs {
+    float* depth;           // (rays)      sum_j w_j t_j
+    float* opacity;         // (rays)      sum_j w_j
+    float* weights;         // (rays, S)   w_j = alpha_j T_j
+    float* rgba;            // (rays*S, 4) sigmoid(rgb), ReLU(sigma)
+    const float* sample_t;  // (rays, S) or NULL
+};
+}  // namespace comp
+// fused_render with the MAPS instantiations (lnerf_k16_maps.hip, lnerf_render_maps.hip): out.acc_color and,
+// with b.target, out.loss as fused_render's; b.target may be NULL (no loss reduction is launched then)
+void fused_render_maps(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b,
+                       const lnerf_outputs& out, const comp::MapsArgs& maps, hipStream_t s, int flags,
+                       hipEvent_t* ev);
+void k16_launch_maps(const FusedPlan& p, const lnerf_batch& b, const lnerf_outputs& out, const comp::MapsArgs& maps,
+                     hipStream_t s);
+void kr_launch_maps(const FusedPlan& p, const lnerf_batch& b, const lnerf_outputs& out, const comp::MapsArgs& maps,
+                    hipStream_t s);
+// generic path: depth_i = sum_j w_ij t_ij and opacity_i = sum_j w_ij per ray, summed sequentially in
+// j (loma's order); t = sample_t (rays, S), or ray_depth(j) when it is NULL (RAYS input). depth /
+// opacity nullable.
+void k_ray_maps(const float* wsamp, const float* sample_t, int rays, int S, float near_t, float far_t,
+                float* depth, float* opacity, hipStream_t s);
+
 }  // namespace lnerf

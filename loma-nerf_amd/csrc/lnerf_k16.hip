@@ -27,6 +27,14 @@
 
 #include <utility>
 
+// LNERF_MAPS_TU: lnerf_k16_maps.hip compiles this file again for the MAPS instantiations alone
+// (k16_launch_maps), in an object of their own: the compiler's output for a kernel depends on what else
+// its translation unit instantiates (lnerf_render.hip), and training and lnerf_render
+// keep the instruction streams they had.
+#ifndef LNERF_MAPS_TU
+#define LNERF_MAPS_TU 0
+#endif
+
 namespace lnerf {
 
 namespace {
@@ -39,7 +47,7 @@ typedef _Float16 hf8 __attribute__((ext_vector_type(8)));
 // per CU) or 4 (256 threads, a 64-sample tile, two workgroups per CU: the two waves of a SIMD
 // then belong to different workgroups, so one's barrier waits, epilogues and compositing run
 // beside the other's MFMAs instead of in lockstep with them)
-constexpr int kWaves = 8;                     // the most waves per workgroup
+[[maybe_unused]] constexpr int kWaves = 8;    // the most waves per workgroup
 constexpr int kMaxChunks = 2 * kMaxLayers * 8 + 1;   // <= 2 passes x 8 k-steps per layer + 1 end
 constexpr int kMaxT = 16;                     // 16-feature tiles per 256-wide layer
 constexpr int kCompBytes = 2688 * 4;          // composite_tile's scratch (comp[0, 2688))
@@ -120,6 +128,10 @@ struct K16Args {
     int nout;          // head outputs (the mlp_fit head's width)
     int* guard;        // PL = 2 training, nullable: set when a hidden G row fails the floor (kGuardExp)
     const int* gate;   // nullable: the launch exits at once unless *gate != 0 (the guard's re-run)
+#if LNERF_MAPS_TU
+    comp::MapsArgs maps;   // the render maps (the MAPS object only: the plain object's kernel-argument
+                           // segment keeps its size, which the kernels' code refers to)
+#endif
 };
 
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
@@ -917,7 +929,10 @@ __device__ __forceinline__ void zero_tiles(fx4 (&t)[kMaxT]) {
 // A group's logical wave lw = wave NG + group owns samples 16 lw ..+15 of the tile: every slab,
 // shift word, mask word and per-wave minimum keeps the (8, 1) layout, so k2 and the mask readback
 // see the same data whatever NG.
-template <int HT, int PL, int NW, int NG = 1>
+// MAPS (lnerf_render_maps, launched forward-only): the compositing also writes the render maps a.maps
+// and takes a NULL target. The rest of the kernel, the reverse chain included, is the same source: every
+// kernel of this name carries the slab stores tests/test_isa.py audits.
+template <int HT, int PL, int NW, int NG = 1, bool MAPS = false>
 __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NG == 2 ? 1 : 2, NG == 2 ? 1 : 2)))
 k16_fwd_bwd_kernel(K16Args a) {
     using R = Ring<PL, NW, NG>;
@@ -1094,6 +1109,9 @@ k16_fwd_bwd_kernel(K16Args a) {
 
     // ---- rendering + loss + rendering reverse (one thread per sample, scans along rays) ----
     if (a.head_fit) comp::fit_tile(a, wg, comp, rayloss, st, a.nout);
+#if LNERF_MAPS_TU
+    else if constexpr (MAPS) comp::composite_tile_wave<comp::kTileSamples, true>(a, wg, comp, rayloss, false, a.maps);
+#endif
     else if (LNERF_K16_WAVECOMP) comp::composite_tile_wave<comp::kTileSamples>(a, wg, comp, rayloss, st);
     else comp::composite_tile(a, wg, comp, rayloss, st);
     __syncthreads();
@@ -1234,6 +1252,7 @@ k16_fwd_bwd_kernel(K16Args a) {
 #endif
 }
 
+#if !LNERF_MAPS_TU   // (the packing, the mask readback and the knobs belong to the plain object)
 // ---- weight packing: per layer and pass, chunk s = [o][plane][lane 64][8 x bf16] -----------
 // forward:  A[m = out 16o + (lane & 15)][k = 8g + j] = W[phi(s, g, j)][16o + m]
 // backward: A[m = in  16o + (lane & 15)][k = 8g + j] = W[16o + m][phi(s, g, j)]
@@ -1380,8 +1399,11 @@ __global__ void k16_masks_kernel(const unsigned long long* __restrict__ mask_g, 
     out[idx] = (unsigned char)(lo | (hi << 4));
 }
 
+#endif   // !LNERF_MAPS_TU
+
 }  // namespace
 
+#if !LNERF_MAPS_TU
 // Compile-time settings of this object that differ from the product build (lnerf_build_knobs):
 // 0 for the shipped library; an A/B variant built with -D... reports which knob it moved.
 unsigned k16_build_knobs() {
@@ -1444,7 +1466,19 @@ void k16_pack(const FusedPlan& p, const float* ws, const float* bs, hipStream_t 
 
 void k16_launch(const FusedPlan& p, const lnerf_batch& b, float seed, const lnerf_outputs& out,
                 bool want_grad, hipStream_t s) {
+#else
+// k16's forward with the MAPS compositing (lnerf_render_maps): the same launch as k16_launch without
+// gradients, on the MAPS instantiations
+void k16_launch_maps(const FusedPlan& p, const lnerf_batch& b, const lnerf_outputs& out, const comp::MapsArgs& maps,
+                     hipStream_t s) {
+    const float seed = 1.0f;
+    const bool want_grad = false;
+#endif
+    constexpr bool kMaps = LNERF_MAPS_TU != 0;
     K16Args a{};
+#if LNERF_MAPS_TU
+    a.maps = maps;
+#endif
     a.L = p.L;
     for (int l = 0; l < p.L; ++l) {
         a.ks_f[l] = p.ks16_f[l];
@@ -1514,25 +1548,25 @@ void k16_launch(const FusedPlan& p, const lnerf_batch& b, float seed, const lner
         // a zero entry past the end (the kernel looks one chunk ahead): a{} zeroed it
     }
     static_assert(sizeof(K16Args) <= 4096, "kernel arguments");
-#if LNERF_K16_G2
+#if LNERF_K16_G2 && !LNERF_MAPS_TU
     // two 16-sample groups per wave, one wave per SIMD (fp16x3, 256-wide hidden layers, 128-sample tiles)
     if (p.x6 == 2 && p.tile == 128 && p.ht16 == 16) {
         k16_fwd_bwd_kernel<16, 2, 4, 2><<<p.num_wg, 256, 0, s>>>(a);
         return;
     }
 #endif
-#ifdef LNERF_K16_ONLY_16_2   // compile-time experiments: one instantiation
+#if defined(LNERF_K16_ONLY_16_2) && !LNERF_MAPS_TU   // compile-time experiments: one instantiation
     if (p.tile == 64) k16_fwd_bwd_kernel<16, 2, 4><<<p.num_wg, 256, 0, s>>>(a);
     else k16_fwd_bwd_kernel<16, 2, 8><<<p.num_wg, 512, 0, s>>>(a);
     return;
 #endif
 // bf16x6 (three planes) always runs the 8-wave workgroup (its ring does not fit two per CU)
 #define LNERF_K16_LAUNCH(HT)                                                                 \
-    if (p.x6 == 3) k16_fwd_bwd_kernel<HT, 3, 8><<<p.num_wg, 512, 0, s>>>(a);                 \
-    else if (p.tile == 64 && p.x6 == 2) k16_fwd_bwd_kernel<HT, 2, 4><<<p.num_wg, 256, 0, s>>>(a); \
-    else if (p.tile == 64) k16_fwd_bwd_kernel<HT, 1, 4><<<p.num_wg, 256, 0, s>>>(a);         \
-    else if (p.x6 == 2) k16_fwd_bwd_kernel<HT, 2, 8><<<p.num_wg, 512, 0, s>>>(a);            \
-    else k16_fwd_bwd_kernel<HT, 1, 8><<<p.num_wg, 512, 0, s>>>(a);
+    if (p.x6 == 3) k16_fwd_bwd_kernel<HT, 3, 8, 1, kMaps><<<p.num_wg, 512, 0, s>>>(a);                 \
+    else if (p.tile == 64 && p.x6 == 2) k16_fwd_bwd_kernel<HT, 2, 4, 1, kMaps><<<p.num_wg, 256, 0, s>>>(a); \
+    else if (p.tile == 64) k16_fwd_bwd_kernel<HT, 1, 4, 1, kMaps><<<p.num_wg, 256, 0, s>>>(a);         \
+    else if (p.x6 == 2) k16_fwd_bwd_kernel<HT, 2, 8, 1, kMaps><<<p.num_wg, 512, 0, s>>>(a);            \
+    else k16_fwd_bwd_kernel<HT, 1, 8, 1, kMaps><<<p.num_wg, 512, 0, s>>>(a);
     switch (p.ht16) {
         case 1: LNERF_K16_LAUNCH(1) break;
         case 2: LNERF_K16_LAUNCH(2) break;

@@ -26,6 +26,14 @@
 
 #include <utility>
 
+// LNERF_MAPS_TU: lnerf_render_maps.hip compiles this file again for the MAPS instantiations alone
+// (kr_launch_maps). They live in an object of their own because the compiler's output for a kernel
+// depends on what else its translation unit instantiates: with both sets in one object the plain
+// kernels' scalar code in the MFMA loop came out different.
+#ifndef LNERF_MAPS_TU
+#define LNERF_MAPS_TU 0
+#endif
+
 namespace lnerf {
 
 namespace {
@@ -85,6 +93,10 @@ struct KrArgs {
     float* d_dists;
     float* d_target;
     float seed;
+#if LNERF_MAPS_TU
+    comp::MapsArgs maps;       // the render maps (the MAPS object only: the plain object's
+                               // kernel-argument segment keeps its size)
+#endif
 };
 
 // ---- optional in-kernel phase timing (-DLNERF_PROF=1, `make prof`, never in the product build):
@@ -317,7 +329,9 @@ __device__ __forceinline__ void kr_epilogue(const float* bl, const fx4 (&acc)[kG
     }
 }
 
-template <int HT>
+// MAPS (lnerf_render_maps): the compositing also writes the render maps a.maps. The MFMA loop is the
+// same, and its accumulators are dead when the compositing starts.
+template <int HT, bool MAPS = false>
 __global__ void __launch_bounds__(64 * kWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))
 kr_fwd_kernel(KrArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[kLds];
@@ -428,7 +442,11 @@ kr_fwd_kernel(KrArgs a) {
     KR_PROF_ADD(kRpLoop, t_loop);
     KR_PROF_T(t_c);
     __syncthreads();
-    comp::composite_fwd_wave<kTile>(a, wg, comp, rayloss);
+#if LNERF_MAPS_TU
+    if constexpr (MAPS) comp::composite_fwd_wave<kTile, true>(a, wg, comp, rayloss, a.maps);
+    else
+#endif
+        comp::composite_fwd_wave<kTile>(a, wg, comp, rayloss);
     __syncthreads();
     if (tid == 0) {
         float lsum = 0.0f;
@@ -445,6 +463,7 @@ kr_fwd_kernel(KrArgs a) {
 
 }  // namespace
 
+#if !LNERF_MAPS_TU
 // plain bf16, the NeRF head, whole rays of <= 128 samples, a layer-0 input of <= 64 features
 // (PE with F <= 10); anything else renders on k16's forward
 // compile-time settings of this object that differ from the product build (lnerf_build_knobs)
@@ -464,7 +483,15 @@ int kr_num_wg(const FusedPlan& p) {
 }
 
 void kr_launch(const FusedPlan& p, const lnerf_batch& b, const lnerf_outputs& out, hipStream_t s) {
+#else
+void kr_launch_maps(const FusedPlan& p, const lnerf_batch& b, const lnerf_outputs& out, const comp::MapsArgs& maps,
+                    hipStream_t s) {
+#endif
+    constexpr bool kMaps = LNERF_MAPS_TU != 0;
     KrArgs a{};
+#if LNERF_MAPS_TU
+    a.maps = maps;
+#endif
     a.L = p.L;
     for (int l = 0; l < p.L; ++l) a.ks[l] = p.ks16_f[l];
     a.k0 = p.k[0];
@@ -499,11 +526,11 @@ void kr_launch(const FusedPlan& p, const lnerf_batch& b, const lnerf_outputs& ou
     static_assert(sizeof(KrArgs) <= 4096, "kernel arguments");
     const int grid = kr_num_wg(p);
     switch (p.ht16) {
-        case 1: kr_fwd_kernel<1><<<grid, 64 * kWaves, 0, s>>>(a); break;
-        case 2: kr_fwd_kernel<2><<<grid, 64 * kWaves, 0, s>>>(a); break;
-        case 4: kr_fwd_kernel<4><<<grid, 64 * kWaves, 0, s>>>(a); break;
-        case 8: kr_fwd_kernel<8><<<grid, 64 * kWaves, 0, s>>>(a); break;
-        default: kr_fwd_kernel<16><<<grid, 64 * kWaves, 0, s>>>(a); break;
+        case 1: kr_fwd_kernel<1, kMaps><<<grid, 64 * kWaves, 0, s>>>(a); break;
+        case 2: kr_fwd_kernel<2, kMaps><<<grid, 64 * kWaves, 0, s>>>(a); break;
+        case 4: kr_fwd_kernel<4, kMaps><<<grid, 64 * kWaves, 0, s>>>(a); break;
+        case 8: kr_fwd_kernel<8, kMaps><<<grid, 64 * kWaves, 0, s>>>(a); break;
+        default: kr_fwd_kernel<16, kMaps><<<grid, 64 * kWaves, 0, s>>>(a); break;
     }
 #if LNERF_PROF
     {

@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "lnerf_adam_update", "lnerf_ctx_timings", "lnerf_get_rays", "lnerf_ctx_last_path",
     "lnerf_ctx_set_option", "lnerf_ctx_relu_masks", "lnerf_build_knobs", "lnerf_ctx_exceptional_rows",
     "lnerf_ctx_guard_fired", "lnerf_input_grad", "lnerf_pose_grad", "lnerf_ctx_workspace_used",
+    "lnerf_render_maps",
 ]
 
 # lnerf_ctx_last_path bits
@@ -60,6 +61,7 @@ PATH_K32 = 16      # reserved (k32, removed in round 4)
 PATH_K16_W4 = 32
 PATH_KR = 64       # the render ran kr (lnerf_render.hip)
 PATH_A24 = 128      # training kept the activation slabs as int24 (fp16x3)
+PATH_MAPS = 1024    # lnerf_render_maps: the MAPS instantiations (bits 8-9 hold the plane count)
 
 
 class LnerfMLP(ctypes.Structure):
@@ -77,6 +79,11 @@ class LnerfOutputs(ctypes.Structure):
     _fields_ = [("loss", ctypes.c_void_p), ("acc_color", ctypes.c_void_p),
                 ("d_ws", ctypes.c_void_p), ("d_bs", ctypes.c_void_p), ("d_x", ctypes.c_void_p),
                 ("d_dists", ctypes.c_void_p), ("d_target", ctypes.c_void_p)]
+
+
+class LnerfRenderOutputs(ctypes.Structure):
+    _fields_ = [("acc_color", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("opacity", ctypes.c_void_p),
+                ("weights", ctypes.c_void_p), ("rgba", ctypes.c_void_p), ("loss", ctypes.c_void_p)]
 
 
 _LIB = None
@@ -184,6 +191,11 @@ def configure(lib: ctypes.CDLL) -> None:
         lib.lnerf_pose_grad.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p,
                                         ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         lib.lnerf_pose_grad.restype = ctypes.c_int
+    if hasattr(lib, "lnerf_render_maps"):   # (older in-tree A/B builds lack the render maps)
+        lib.lnerf_render_maps.argtypes = [ctypes.c_void_p, ctypes.POINTER(LnerfMLP), ctypes.c_void_p,
+                                          ctypes.c_void_p, ctypes.POINTER(LnerfBatch), ctypes.c_void_p,
+                                          ctypes.c_int, ctypes.POINTER(LnerfRenderOutputs), ctypes.c_void_p]
+        lib.lnerf_render_maps.restype = ctypes.c_int
     for name in ("lnerf_ctx_timings", "lnerf_ctx_last_path", "lnerf_ctx_set_option", "lnerf_ctx_relu_masks",
                  "lnerf_ctx_exceptional_rows", "lnerf_ctx_guard_fired",
                  "lnerf_ctx_create", "lnerf_train_step", "lnerf_render",
@@ -225,6 +237,20 @@ class StepResult:
     d_target: object = None
     d_x: object = None
     d_input: object = None   # want_dinput: the gradient with respect to x, in x's shape
+
+
+@dataclass
+class RenderMaps:
+    """Engine.render_maps' result: device tensors, None where not asked for."""
+    color: object = None     # (rays, 3)
+    depth: object = None     # (rays)      sum_j w_j t_j, not divided by the opacity
+    opacity: object = None   # (rays)      sum_j w_j
+    weights: object = None   # (rays, S)   w_j = alpha_j T_j (the reference's inclusive transmittance)
+    rgba: object = None      # (rays*S, 4) sigmoid(rgb), ReLU(sigma)
+    loss: object = None      # scalar; only with a target
+
+
+MAP_NAMES = ("color", "depth", "opacity", "weights", "rgba", "loss")
 
 
 class Engine:
@@ -348,6 +374,40 @@ class Engine:
             raise RuntimeError(f"lnerf_render: {last_error()}")
         return loss[0], acc
 
+    def render_maps(self, mlp: LnerfMLP, ws, bs, x, dists, target=None, *, samples: int,
+                    input_mode: int = INPUT_POINTS, num_freqs: int = 5, near: float = 2.0,
+                    far: float = 6.0, sample_t=None, flags: int = 0,
+                    want=("color", "depth", "opacity"), buffers=None) -> RenderMaps:
+        """lnerf_render_maps: the forward render with the colour, the expected depth sum_j w_j t_j, the
+        opacity sum_j w_j, the per-sample weights and rgba, and (with a target) the loss; `want` names
+        the maps to produce (MAP_NAMES), every other field of the result is None. No target is needed.
+        INPUT_RAYS: the depths are the engine's own linspace(near, far, S) and sample_t must be None;
+        INPUT_POINTS / INPUT_ENCODED: sample_t (rays, S) is required for "depth". `buffers` may map a
+        name to a preallocated float32 device tensor to write into. An extension (lnerf.h)."""
+        torch = self.torch
+        unknown = set(want) - set(MAP_NAMES)
+        if unknown:
+            raise ValueError(f"unknown maps {sorted(unknown)} (known: {MAP_NAMES})")
+        rays = x.shape[0] if input_mode == INPUT_RAYS else x.shape[0] // samples
+        b = LnerfBatch(rays, samples, input_mode, num_freqs, x.data_ptr(),
+                       None if dists is None else dists.data_ptr(),
+                       None if target is None else target.data_ptr(), float(near), float(far))
+        shapes = dict(color=(rays, 3), depth=(rays,), opacity=(rays,), weights=(rays, samples),
+                      rgba=(rays * samples, 4), loss=(1,))
+        bufs = {}
+        for name in want:
+            t = (buffers or {}).get(name)
+            bufs[name] = t if t is not None else torch.empty(shapes[name], dtype=torch.float32, device=x.device)
+        o = LnerfRenderOutputs(_ptr(bufs.get("color")), _ptr(bufs.get("depth")), _ptr(bufs.get("opacity")),
+                               _ptr(bufs.get("weights")), _ptr(bufs.get("rgba")), _ptr(bufs.get("loss")))
+        rc = self.lib.lnerf_render_maps(self.ctx, ctypes.byref(mlp), ws.data_ptr(), bs.data_ptr(),
+                                        ctypes.byref(b), _ptr(sample_t), flags, ctypes.byref(o), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_render_maps: {last_error()}")
+        if "loss" in bufs:
+            bufs["loss"] = bufs["loss"][0]
+        return RenderMaps(**bufs)
+
     def get_rays(self, width: int, K, c2w):
         """train_nerf.py:23-62 on the device: (width*width, 6) float32 rays [o, d]."""
         import numpy as np
@@ -436,10 +496,13 @@ class Engine:
         v = self.lib.lnerf_ctx_last_path(self.ctx)
         if v < 0:
             raise RuntimeError(f"lnerf_ctx_last_path: {last_error()}")
-        return dict(generic=bool(v & PATH_GENERIC), fused=bool(v & PATH_FUSED),
-                    k16=bool(v & PATH_K16), dw16=bool(v & PATH_DW16), k16_w4=bool(v & PATH_K16_W4),
-                    kr=bool(v & PATH_KR), a24=bool(v & PATH_A24),
-                    planes=(v >> 8) & 3)
+        d = dict(generic=bool(v & PATH_GENERIC), fused=bool(v & PATH_FUSED),
+                 k16=bool(v & PATH_K16), dw16=bool(v & PATH_DW16), k16_w4=bool(v & PATH_K16_W4),
+                 kr=bool(v & PATH_KR), a24=bool(v & PATH_A24),
+                 planes=(v >> 8) & 3)
+        if v & PATH_MAPS:   # only after render_maps: the kernels' bits as after render, plus this key
+            d["maps"] = True
+        return d
 
     def relu_masks(self, L: int, R: int):
         """The last training step's hidden ReLU decisions (k16 path): numpy bool (L-1, R, 256),

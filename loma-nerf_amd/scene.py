@@ -114,6 +114,19 @@ def render_image(engine, mlp, ws, bs, width, K, c2w, samples, num_freqs, near=2.
     return acc
 
 
+def render_maps_image(engine, mlp, ws, bs, width, K, c2w, samples, num_freqs, near=2.0, far=6.0,
+                      flags=0, rays=None, want=("color", "depth", "opacity")):
+    """A novel view with the renderer's standard maps (an extension; the reference renders colour
+    only): get_rays for the full width x width frame and one Engine.render_maps call on
+    LNERF_INPUT_RAYS, no target. Returns lnerf.RenderMaps: color (width*width, 3), depth and opacity
+    (width*width), weights / rgba when `want` names them (device tensors)."""
+    import lnerf
+    if rays is None:
+        rays = engine.get_rays(width, K, c2w)
+    return engine.render_maps(mlp, ws, bs, rays, None, None, samples=samples, input_mode=lnerf.INPUT_RAYS,
+                              num_freqs=num_freqs, near=near, far=far, flags=flags, want=want)
+
+
 def step_flops(shapes):
     """Canonical algorithmic FLOPs per sample: fwd 2KN every layer, bwd dW 2KN
     every layer, bwd dX 2KN for l >= 1."""
