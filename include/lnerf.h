@@ -282,6 +282,61 @@ int lnerf_input_grad(const lnerf_batch* batch, const float* d_encoded, const flo
 int lnerf_pose_grad(int width, const double* K, const int* pixels, int n, const float* d_rays,
                     double* d_c2w, void* stream);
 
+/* ---- Per-ray sample depths -------------------------------------------------------------------
+ * Four free functions on a stream (no context, no workspace) that turn rays plus per-ray depths
+ * into what LNERF_INPUT_POINTS and lnerf_render_maps(..., sample_t, ...) accept, and back. The
+ * reference samples linspace(near, far, S) only (its jitter is a TODO, train_nerf.py:289-294).
+ * All arithmetic is float64 with one rounding to float32 at the store, every sum has a fixed order:
+ * repeated calls give the same bits. All pointers are device pointers. An error returns a negative
+ * code, sets lnerf_last_error and launches and writes nothing; rays == 0 (n == 0) succeeds and
+ * launches nothing. At most 2^31 - 1 values per array. */
+
+/* Stratified jitter of the engine's linspace: sample_t (rays, S) from u (rays, S), e.g. uniform
+ * random numbers of the caller's (the library owns no generator, so results are reproducible).
+ * With g = linspace(near_t, far_t, S) in float64 (the depths LNERF_INPUT_RAYS samples) and the
+ * cell edges lower_j = j ? (g_{j-1} + g_j) / 2 : g_0, upper_j = j < S-1 ? (g_j + g_{j+1}) / 2 : g_{S-1}:
+ * t_j = (float)(lower_j + (upper_j - lower_j) u_j), u clamped to [0, 1], a NaN taken as 0. S == 1
+ * gives near_t. Non-decreasing along each ray. u == NULL is an error.
+ * An extension (no loma counterpart). */
+int lnerf_sample_stratified(int rays, int S, float near_t, float far_t, const float* u,
+                            float* sample_t, void* stream);
+
+/* Hierarchical (importance) sampling: n_fine depths per ray drawn from the coarse pass's weights
+ * (rays, S), as lnerf_render_maps writes them, by inverting their piecewise-linear cdf.
+ *   t_coarse (rays, S), non-decreasing per ray; NULL: (float)linspace(near_t, far_t, S), the depths
+ * lnerf_render_maps reports for RAYS input (near_t / far_t are read only then).
+ *   u (rays, n_fine), clamped as above; NULL: the deterministic u_k = (k + 0.5) / n_fine.
+ *   Per ray, in float64: bin edges m_i = (t_i + t_{i+1}) / 2, i = 0..S-2; p_i = w_{i+1} + 1e-5,
+ * i = 0..S-3 (the interior weights; a NaN, infinite or negative weight counts as 0); cdf_0 = 0,
+ * cdf_{i+1} = (sum_{k<=i} p_k) / sum p, the last exactly 1. For each u: bin i = the largest index
+ * with cdf_i <= u, at most S-3, and z = m_i + (u - cdf_i) / (cdf_{i+1} - cdf_i) (m_{i+1} - m_i),
+ * rounded once to float32 (and moved one float32 inward should that rounding leave [m_0, m_{S-2}]).
+ * Every output is finite and inside [m_0, m_{S-2}] whatever the weights hold.
+ *   t_fine (rays, n_fine), in u's order. t_all (rays, S + n_fine): the ray's coarse and fine depths
+ * merged in non-decreasing order of their float32 values (ties coarse first, then fine; equal
+ * values have equal bits, so the order among them cannot be seen), i.e.
+ * sort(concat(t_coarse, t_fine)) bit for bit. Either may be NULL, not both.
+ *   3 <= S <= 1024 and 1 <= n_fine <= 1024. An extension (no loma counterpart). */
+int lnerf_sample_importance(int rays, int S, const float* t_coarse, float near_t, float far_t,
+                            const float* weights, int n_fine, const float* u, float* t_fine,
+                            float* t_all, void* stream);
+
+/* The sample points and dists of rays (n, 6) = [o, d] at per-ray depths sample_t (n, S):
+ * points[i S + j][c] = (float)((double)o_c + (double)d_c (double)t_ij), (n*S, 3), and
+ * dists[i][j] = (float)((double)t_{i,j+1} - (double)t_ij), the last 1e8f (train_nerf.py:306-311),
+ * (n, S): ready for LNERF_INPUT_POINTS, with sample_t for lnerf_render_maps. Either output may be
+ * NULL. An extension (no loma counterpart). */
+int lnerf_ray_points(const float* rays, int n, int S, const float* sample_t, float* points,
+                     float* dists, void* stream);
+
+/* The reverse of lnerf_ray_points with respect to the rays: d_rays (n, 6) = [sum_j d_p[j],
+ * sum_j t_ij d_p[j]] from d_points (n*S, 3) -- what LNERF_WANT_DINPUT returns for POINTS input --
+ * summed in float64 in a fixed order, rounded once; feeds lnerf_pose_grad unchanged. `scale`
+ * (nullable) is a device scalar multiplied in, as in lnerf_input_grad. (The depths are inputs of
+ * their own: there is no gradient with respect to sample_t.) An extension (no loma counterpart). */
+int lnerf_ray_points_grad(int n, int S, const float* sample_t, const float* d_points,
+                          const float* scale, float* d_rays, void* stream);
+
 /* Forward only (eval render, train_nerf.py:616-661, which always has a target image): acc_color
  * and the loss against batch->target. batch->target is required (NULL: an error, nothing is
  * launched or written); the loss is always computed and written to out->loss unless that is NULL.

@@ -830,6 +830,70 @@ extern "C" int lnerf_pose_grad(int width, const double* K, const int* pixels, in
     });
 }
 
+// ---- per-ray sample depths (lnerf_sampling.hip): free functions on a stream, no context ----------
+static void check_rows(const char* what, int rays, int per_ray) {
+    if (rays < 0) fail("%s: negative ray count %d", what, rays);
+    if ((long long)rays * per_ray > (long long)std::numeric_limits<int>::max())
+        fail("%s: more than 2^31 - 1 values", what);
+}
+
+extern "C" int lnerf_sample_stratified(int rays, int S, float near_t, float far_t, const float* u,
+                                       float* sample_t, void* stream) {
+    return guard_int([&]() {
+        if (!u) fail("lnerf_sample_stratified: u is NULL (the library owns no random numbers)");
+        if (!sample_t) fail("lnerf_sample_stratified: sample_t is NULL");
+        if (S < 1) fail("lnerf_sample_stratified: S = %d, need at least 1", S);
+        check_rows("lnerf_sample_stratified", rays, S);
+        if (rays == 0) return;
+        need_device();
+        k_sample_stratified(rays, S, near_t, far_t, u, sample_t, (hipStream_t)stream);
+        check_launch("lnerf_sample_stratified");
+    });
+}
+
+extern "C" int lnerf_sample_importance(int rays, int S, const float* t_coarse, float near_t, float far_t,
+                                       const float* weights, int n_fine, const float* u, float* t_fine,
+                                       float* t_all, void* stream) {
+    return guard_int([&]() {
+        if (S < 3 || S > 1024) fail("lnerf_sample_importance: S = %d outside 3..1024", S);
+        if (n_fine < 1 || n_fine > 1024) fail("lnerf_sample_importance: n_fine = %d outside 1..1024", n_fine);
+        if (!weights) fail("lnerf_sample_importance: weights is NULL");
+        if (!t_fine && !t_all) fail("lnerf_sample_importance: t_fine and t_all are both NULL");
+        check_rows("lnerf_sample_importance", rays, S + n_fine);
+        if (rays == 0) return;
+        need_device();
+        k_sample_importance(rays, S, t_coarse, near_t, far_t, weights, n_fine, u, t_fine, t_all,
+                            (hipStream_t)stream);
+        check_launch("lnerf_sample_importance");
+    });
+}
+
+extern "C" int lnerf_ray_points(const float* rays, int n, int S, const float* sample_t, float* points,
+                                float* dists, void* stream) {
+    return guard_int([&]() {
+        if (!rays || !sample_t) fail("lnerf_ray_points: null argument");
+        if (S < 1) fail("lnerf_ray_points: S = %d, need at least 1", S);
+        check_rows("lnerf_ray_points", n, S);
+        if (n == 0 || (!points && !dists)) return;
+        need_device();
+        k_ray_points(rays, n, S, sample_t, points, dists, (hipStream_t)stream);
+        check_launch("lnerf_ray_points");
+    });
+}
+
+extern "C" int lnerf_ray_points_grad(int n, int S, const float* sample_t, const float* d_points,
+                                     const float* scale, float* d_rays, void* stream) {
+    return guard_int([&]() {
+        if (!sample_t || !d_points || !d_rays) fail("lnerf_ray_points_grad: null argument");
+        if (S < 1) fail("lnerf_ray_points_grad: S = %d, need at least 1", S);
+        check_rows("lnerf_ray_points_grad", n, S);
+        if (n == 0) return;
+        need_device();
+        k_ray_points_grad(n, S, sample_t, d_points, scale, d_rays, (hipStream_t)stream);
+        check_launch("lnerf_ray_points_grad");
+    });
+}
+
 extern "C" int lnerf_render(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* ws, const float* bs,
                             const lnerf_batch* batch, int flags, const lnerf_outputs* out,
                             void* stream) {

@@ -215,6 +215,16 @@ void k_input_grad(const lnerf_batch& b, const float* dE, const float* scale, flo
 int pose_grad_parts(int n);
 void k_pose_grad(int width, const double* K, const int* pixels, int n, const float* d_rays, double* part,
                  double* d_c2w, hipStream_t s);
+// Per-ray sample depths (lnerf_sampling.hip); include/lnerf.h states what each computes. The callers
+// have validated the arguments (rays >= 1; importance: 3 <= S <= 1024, 1 <= n_fine <= 1024).
+void k_sample_stratified(int rays, int S, float near_t, float far_t, const float* u, float* sample_t,
+                         hipStream_t s);
+void k_sample_importance(int rays, int S, const float* t_coarse, float near_t, float far_t, const float* weights,
+                         int n_fine, const float* u, float* t_fine, float* t_all, hipStream_t s);
+void k_ray_points(const float* rays, int n, int S, const float* sample_t, float* points, float* dists,
+                  hipStream_t s);
+void k_ray_points_grad(int n, int S, const float* sample_t, const float* d_points, const float* scale,
+                       float* d_rays, hipStream_t s);
 
 // ----------------------------------------------------------------------------------------------
 // Fused MFMA path (the throughput path). See DESIGN.md "Kernels".

@@ -49,7 +49,8 @@ EXPORTED_SYMBOLS = [
     "lnerf_adam_update", "lnerf_ctx_timings", "lnerf_get_rays", "lnerf_ctx_last_path",
     "lnerf_ctx_set_option", "lnerf_ctx_relu_masks", "lnerf_build_knobs", "lnerf_ctx_exceptional_rows",
     "lnerf_ctx_guard_fired", "lnerf_input_grad", "lnerf_pose_grad", "lnerf_ctx_workspace_used",
-    "lnerf_render_maps",
+    "lnerf_render_maps", "lnerf_sample_stratified", "lnerf_sample_importance", "lnerf_ray_points",
+    "lnerf_ray_points_grad",
 ]
 
 # lnerf_ctx_last_path bits
@@ -196,6 +197,15 @@ def configure(lib: ctypes.CDLL) -> None:
                                           ctypes.c_void_p, ctypes.POINTER(LnerfBatch), ctypes.c_void_p,
                                           ctypes.c_int, ctypes.POINTER(LnerfRenderOutputs), ctypes.c_void_p]
         lib.lnerf_render_maps.restype = ctypes.c_int
+    if hasattr(lib, "lnerf_sample_importance"):   # (older in-tree A/B builds lack the sampling kernels)
+        vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+        lib.lnerf_sample_stratified.argtypes = [ci, ci, cf, cf, vp, vp, vp]
+        lib.lnerf_sample_importance.argtypes = [ci, ci, vp, cf, cf, vp, ci, vp, vp, vp, vp]
+        lib.lnerf_ray_points.argtypes = [vp, ci, ci, vp, vp, vp, vp]
+        lib.lnerf_ray_points_grad.argtypes = [ci, ci, vp, vp, vp, vp, vp]
+        for name in ("lnerf_sample_stratified", "lnerf_sample_importance", "lnerf_ray_points",
+                     "lnerf_ray_points_grad"):
+            getattr(lib, name).restype = ctypes.c_int
     for name in ("lnerf_ctx_timings", "lnerf_ctx_last_path", "lnerf_ctx_set_option", "lnerf_ctx_relu_masks",
                  "lnerf_ctx_exceptional_rows", "lnerf_ctx_guard_fired",
                  "lnerf_ctx_create", "lnerf_train_step", "lnerf_render",
@@ -455,6 +465,96 @@ class Engine:
                                       d_rays.shape[0], _ptr(d_rays), _ptr(out), self._stream())
         if rc != 0:
             raise RuntimeError(f"lnerf_pose_grad: {last_error()}")
+        return out
+
+    def _f32(self, name, t, shape=None):
+        """`t` must be a contiguous float32 tensor on this engine's device (of `shape`, if given)."""
+        torch = self.torch
+        if not torch.is_tensor(t) or t.dtype != torch.float32:
+            raise ValueError(f"{name} must be a float32 tensor")
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"{name} must live on cuda:{self.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} is {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+
+    def sample_stratified(self, rays: int, samples: int, u, near: float = 2.0, far: float = 6.0):
+        """lnerf_sample_stratified: (rays, samples) float32 depths, one per cell of
+        linspace(near, far, samples), placed inside its cell by u (rays, samples) in [0, 1] -- the
+        caller's random numbers (e.g. torch.rand); non-decreasing along each ray."""
+        self._f32("u", u, (rays, samples))
+        out = self.torch.empty(rays, samples, dtype=self.torch.float32, device=u.device)
+        rc = self.lib.lnerf_sample_stratified(rays, samples, float(near), float(far), _ptr(u), _ptr(out),
+                                              self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_sample_stratified: {last_error()}")
+        return out
+
+    def sample_importance(self, weights, n_fine: int, t_coarse=None, u=None, near: float = 2.0,
+                          far: float = 6.0, want=("fine", "all")):
+        """lnerf_sample_importance: n_fine depths per ray drawn from the coarse pass's `weights`
+        (rays, S), as render_maps(want=("weights",)) returns them. t_coarse (rays, S) are the coarse
+        depths (None: the engine's linspace(near, far, S)), u (rays, n_fine) the caller's random
+        numbers (None: the deterministic (k + 0.5) / n_fine). Returns (t_fine (rays, n_fine) in u's
+        order, t_all (rays, S + n_fine) = the coarse and fine depths merged in order); an entry `want`
+        does not name is None."""
+        unknown = set(want) - {"fine", "all"}
+        if unknown or not want:
+            raise ValueError(f"want must name 'fine' and / or 'all', got {tuple(want)}")
+        if weights.dim() != 2:
+            raise ValueError(f"weights is {tuple(weights.shape)}, expected (rays, S)")
+        rays, S = weights.shape
+        self._f32("weights", weights)
+        if t_coarse is not None:
+            self._f32("t_coarse", t_coarse, (rays, S))
+        if u is not None:
+            self._f32("u", u, (rays, n_fine))
+        torch = self.torch
+        fine = torch.empty(rays, n_fine, dtype=torch.float32, device=weights.device) if "fine" in want else None
+        both = torch.empty(rays, S + n_fine, dtype=torch.float32, device=weights.device) if "all" in want else None
+        rc = self.lib.lnerf_sample_importance(rays, S, _ptr(t_coarse), float(near), float(far), _ptr(weights),
+                                              int(n_fine), _ptr(u), _ptr(fine), _ptr(both), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_sample_importance: {last_error()}")
+        return fine, both
+
+    def ray_points(self, rays, sample_t):
+        """lnerf_ray_points: (points (n*S, 3), dists (n, S)) of rays (n, 6) = [o, d] at the per-ray
+        depths sample_t (n, S): points o + d t and dists = [diff(t), 1e8], ready for INPUT_POINTS
+        (and sample_t for render_maps)."""
+        if sample_t.dim() != 2:
+            raise ValueError(f"sample_t is {tuple(sample_t.shape)}, expected (rays, S)")
+        n, S = sample_t.shape
+        self._f32("sample_t", sample_t)
+        self._f32("rays", rays, (n, 6))
+        torch = self.torch
+        points = torch.empty(n * S, 3, dtype=torch.float32, device=rays.device)
+        dists = torch.empty(n, S, dtype=torch.float32, device=rays.device)
+        rc = self.lib.lnerf_ray_points(_ptr(rays), n, S, _ptr(sample_t), _ptr(points), _ptr(dists), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_ray_points: {last_error()}")
+        return points, dists
+
+    def ray_points_grad(self, sample_t, d_points, scale=None):
+        """lnerf_ray_points_grad, the reverse of ray_points: d_rays (n, 6) = [sum_j d_p, sum_j t_j d_p]
+        from d_points (n*S, 3) (StepResult.d_input of an INPUT_POINTS step); feeds pose_grad. `scale`
+        is an optional float32 device scalar multiplied in."""
+        if sample_t.dim() != 2:
+            raise ValueError(f"sample_t is {tuple(sample_t.shape)}, expected (rays, S)")
+        n, S = sample_t.shape
+        self._f32("sample_t", sample_t)
+        self._f32("d_points", d_points, (n * S, 3))
+        if scale is not None:
+            self._f32("scale", scale)
+            if scale.numel() != 1:
+                raise ValueError("scale must hold one value")
+        out = self.torch.empty(n, 6, dtype=self.torch.float32, device=d_points.device)
+        rc = self.lib.lnerf_ray_points_grad(n, S, _ptr(sample_t), _ptr(d_points), _ptr(scale), _ptr(out),
+                                            self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_ray_points_grad: {last_error()}")
         return out
 
     def timings(self):

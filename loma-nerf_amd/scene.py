@@ -127,6 +127,29 @@ def render_maps_image(engine, mlp, ws, bs, width, K, c2w, samples, num_freqs, ne
                               num_freqs=num_freqs, near=near, far=far, flags=flags, want=want)
 
 
+def render_hierarchical_image(engine, coarse, fine, width, K, c2w, samples, n_fine, num_freqs, near=2.0,
+                              far=6.0, flags=0, rays=None, u=None, want=("color", "depth", "opacity")):
+    """A novel view with hierarchical sampling (an extension; the reference samples one fixed grid):
+    `coarse` and `fine` are each (mlp, ws, bs). The coarse network renders the frame's rays at
+    linspace(near, far, samples) for its compositing weights, Engine.sample_importance draws n_fine
+    more depths per ray from them (u: optional (rays, n_fine) random numbers, None = the deterministic
+    midpoints), Engine.ray_points turns the merged samples + n_fine depths into points and dists, and
+    the fine network renders those (LNERF_INPUT_POINTS, sample_t = the merged depths). Returns the
+    fine pass's lnerf.RenderMaps (depth included)."""
+    import lnerf
+    if rays is None:
+        rays = engine.get_rays(width, K, c2w)
+    cm, cws, cbs = coarse
+    fm, fws, fbs = fine
+    w = engine.render_maps(cm, cws, cbs, rays, None, None, samples=samples, input_mode=lnerf.INPUT_RAYS,
+                           num_freqs=num_freqs, near=near, far=far, flags=flags, want=("weights",)).weights
+    _, t_all = engine.sample_importance(w, n_fine, u=u, near=near, far=far, want=("all",))
+    points, dists = engine.ray_points(rays, t_all)
+    return engine.render_maps(fm, fws, fbs, points, dists, None, samples=samples + n_fine,
+                              input_mode=lnerf.INPUT_POINTS, num_freqs=num_freqs, sample_t=t_all, flags=flags,
+                              want=want)
+
+
 def step_flops(shapes):
     """Canonical algorithmic FLOPs per sample: fwd 2KN every layer, bwd dW 2KN
     every layer, bwd dX 2KN for l >= 1."""
