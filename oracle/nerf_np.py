@@ -179,7 +179,8 @@ def relu_tie_rays(w: Workload, thresh: float = 5e-7) -> np.ndarray:
 def subset_rays(w: Workload, rays) -> Workload:
     rays = np.asarray(rays, np.int64)
     rows = (rays[:, None] * w.S + np.arange(w.S)[None, :]).ravel()
-    return Workload(w.pts[rays], w.pts32[rays], w.X[rows], w.dists[rays], w.target[rays], w.ws, w.bs,
+    pts, pts32 = (None, None) if w.pts32 is None else (w.pts[rays], w.pts32[rays])   # ENCODED-only workloads
+    return Workload(pts, pts32, w.X[rows], w.dists[rays], w.target[rays], w.ws, w.bs,
                     w.wp, w.bp, w.F, w.S, len(rays))
 
 

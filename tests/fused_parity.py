@@ -42,11 +42,22 @@ def padded(per_layer, shape):
     return out
 
 
-def encoded_input(w, points):
+def encoded_input(w, points, rays32=None):
     import oracle
+    if rays32 is not None:
+        return rays_reference(rays32, w.S, w.F)[0]
     if points:
         return oracle.positional_encoding_3d(w.pts32.astype(np.float64), w.F)
     return np.ascontiguousarray(w.X, np.float32)
+
+
+def rays_reference(rays32, S, F, near=2.0, far=6.0):
+    """What INPUT_RAYS computes from float32 rays [o, d] (train_nerf.py:289-306), as
+    test_gpu_native._rays_reference: float64 points o + d t, the encoding rounded once, dists
+    [diff(t), 1e8] as float32. Returns (X, dists)."""
+    pts, dists = nerf_np.sample_rays(rays32[:, :3].astype(np.float64), rays32[:, 3:].astype(np.float64), S, near, far)
+    X = nerf_np.positional_encoding_3d(pts, F).reshape(-1, 3 + 6 * F)
+    return X, dists.astype(np.float32)
 
 
 def _dev(engine, a):
@@ -54,16 +65,21 @@ def _dev(engine, a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(f"cuda:{engine.device}")
 
 
-def run_fused(engine, w, *, points=True, seed=None, flags=0, want_dx=False):
-    """One GPU training step on workload w; returns its outputs and its ReLU decisions."""
+def run_fused(engine, w, *, points=True, seed=None, flags=0, want_dx=False, rays32=None):
+    """One GPU training step on workload w; returns its outputs and its ReLU decisions. rays32
+    (N, 6) float32 [o, d]: the step runs INPUT_RAYS on them (its own samples and dists) instead of
+    w's points."""
     import lnerf
     import torch
     shapes = [x.shape for x in w.ws]
     mlp = lnerf.make_mlp(shapes, w.wp.shape[1], w.wp.shape[2])
-    x = _dev(engine, w.pts32.reshape(-1, 3) if points else w.X)
-    r = engine.train_step(mlp, _dev(engine, w.wp), _dev(engine, w.bp), x, _dev(engine, w.dists),
-                          _dev(engine, w.target), samples=w.S,
-                          input_mode=lnerf.INPUT_POINTS if points else lnerf.INPUT_ENCODED,
+    if rays32 is not None:
+        x, dists, mode = _dev(engine, rays32), None, lnerf.INPUT_RAYS
+    else:
+        x = _dev(engine, w.pts32.reshape(-1, 3) if points else w.X)
+        dists, mode = _dev(engine, w.dists), lnerf.INPUT_POINTS if points else lnerf.INPUT_ENCODED
+    r = engine.train_step(mlp, _dev(engine, w.wp), _dev(engine, w.bp), x, dists,
+                          _dev(engine, w.target), samples=w.S, input_mode=mode,
                           num_freqs=w.F, seed=seed, flags=lnerf.FAST | flags, want_per_ray=True,
                           want_dx=want_dx)
     torch.cuda.synchronize()
@@ -81,13 +97,16 @@ def run_fused(engine, w, *, points=True, seed=None, flags=0, want_dx=False):
 
 
 def check_fused(engine, w, *, points=True, seed=None, flags=0, want_dx=False, tol64=TOL64,
-                tolc=TOLC, c_oracle=True):
+                tolc=TOLC, c_oracle=True, rays32=None):
+    """rays32: INPUT_RAYS on these float32 rays; the references then take rays_reference's encoding
+    and dists in place of w's."""
     import oracle
-    got = run_fused(engine, w, points=points, seed=seed, flags=flags, want_dx=want_dx)
-    X = encoded_input(w, points)
+    got = run_fused(engine, w, points=points, seed=seed, flags=flags, want_dx=want_dx, rays32=rays32)
+    X = encoded_input(w, points, rays32)
+    dists = w.dists if rays32 is None else rays_reference(rays32, w.S, w.F)[1]
     shapes = [x.shape for x in w.ws]
     # 1. float64 at the GPU's decisions, every ray
-    ref = nerf_np.nerf_forward_backward(X, w.ws, w.bs, w.dists, w.target, w.S, seed=seed,
+    ref = nerf_np.nerf_forward_backward(X, w.ws, w.bs, dists, w.target, w.S, seed=seed,
                                         masks=got["masks"])
     assert abs(got["loss"] - ref["loss"]) <= 1e-6 * abs(ref["loss"]), (got["loss"], ref["loss"])
     assert_close("acc", got["acc"], ref["acc"], **tol64)
@@ -109,7 +128,7 @@ def check_fused(engine, w, *, points=True, seed=None, flags=0, want_dx=False, to
     stats = dict(rays=w.N, flips_vs_f64=flips, worst_flip_margin=worst)
     # 3. the loma-order fp32 oracle on the rays whose decisions agree with its own
     if c_oracle:
-        want = oracle.standard_forward_backward(X, w.wp, w.bp, shapes, w.dists, w.target, w.S,
+        want = oracle.standard_forward_backward(X, w.wp, w.bp, shapes, dists, w.target, w.S,
                                                 seed=seed, dX=want_dx)
         R = w.N * w.S
         bad = np.zeros(R, bool)
@@ -121,9 +140,10 @@ def check_fused(engine, w, *, points=True, seed=None, flags=0, want_dx=False, to
         if len(rays_bad):
             keep = [r for r in range(w.N) if r not in set(rays_bad.tolist())]
             sub = nerf_np.subset_rays(w, keep)
-            g2 = run_fused(engine, sub, points=points, seed=seed, flags=flags, want_dx=want_dx)
-            Xs = encoded_input(sub, points)
-            want = oracle.standard_forward_backward(Xs, sub.wp, sub.bp, shapes, sub.dists, sub.target,
+            rsub = None if rays32 is None else np.ascontiguousarray(rays32[keep])
+            g2 = run_fused(engine, sub, points=points, seed=seed, flags=flags, want_dx=want_dx, rays32=rsub)
+            Xs = encoded_input(sub, points, rsub)
+            want = oracle.standard_forward_backward(Xs, sub.wp, sub.bp, shapes, dists[keep], sub.target,
                                                     sub.S, seed=seed, dX=want_dx)
         assert abs(g2["loss"] - want["loss"]) <= 1e-5 * abs(want["loss"]), (g2["loss"], want["loss"])
         for k in ("acc", "dW", "dB", "d_dists", "d_target") + (("dX",) if want_dx else ()):

@@ -116,6 +116,63 @@ def test_mlp_fit_step_matches_oracle_256x256(engine, fit):
     assert torch.equal(out2, out)
 
 
+HEAD_CASES = [(22, 1, 37), (22, 2, 256), (22, 4, 300), (70, 3, 129), (1, 4, 5)]
+
+
+@pytest.mark.parametrize("k0,n_out,rows", HEAD_CASES)
+def test_mlp_fit_head_widths(engine, k0, n_out, rows):
+    """The fit head at every width it takes (fit_tile zeroes gz for k >= n_out; target, outputs and
+    d_target are (rows, n_out)), on a partial tile, whole tiles, a ragged third tile, a first layer of
+    more than 64 features and the smallest step there is: the assertions and tolerances of
+    test_mlp_fit_step_matches_oracle_256x256, and d_target = -2 seed (o - t). (On the CPU the two
+    references agree within 2.5e-7 of |want| + max|want| on every tensor and 8.6e-7 on the loss, and
+    no layer's dW is empty.)"""
+    import ctypes
+
+    import lnerf
+    import scene
+    import torch
+    shapes, wp, bp = scene.init_mlp(k0, n_out, 3, 16, seed=215)
+    rng = np.random.RandomState(1000 * k0 + 10 * n_out + rows)
+    X = rng.uniform(-1, 1, (rows, k0)).astype(np.float32)
+    T = rng.uniform(0, 1, (rows, n_out)).astype(np.float32)
+    seed = 1.7
+    mlp = lnerf.make_mlp(shapes, wp.shape[1], wp.shape[2])
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+    loss, out, g = engine.mlp_fit_step(mlp, t(wp), t(bp), t(X), t(T), seed=seed, flags=lnerf.FAST)
+    torch.cuda.synchronize()
+    path = engine.last_path()
+    assert path["k16"] and path["dw16"] and path["planes"] == 2, path
+    assert tuple(out.shape) == (rows, n_out)
+    nW = wp.size
+    gd = g.cpu().numpy()
+    got = dict(loss=float(loss), out=out.cpu().numpy(), dW=gd[:nW].reshape(wp.shape), dB=gd[nW:-1].reshape(bp.shape))
+    f64 = f64_fit(X, T, wp, bp, shapes, seed)
+    assert np.abs(f64[2]).max() > 0
+    for ref, tol in ((f64, TOL), (oracle_fit(X, T, wp, bp, shapes, seed), dict(rtol=1e-4, atol_scale=1e-4))):
+        want_loss, want_out, want_dW, want_dB = ref
+        assert abs(got["loss"] - want_loss) <= tol["rtol"] * abs(want_loss), (got["loss"], want_loss)
+        assert_close("outputs", got["out"], want_out, **tol)
+        assert_close("dW", got["dW"], want_dW, **tol)
+        assert_close("dB", got["dB"], want_dB, **tol)
+    # d_target through the raw call (mlp_fit_step does not return it): (rows, n_out), and the rows past
+    # the end of a longer buffer stay as they were
+    Xd, Td, wsd, bsd = t(X), t(T), t(wp), t(bp)
+    _, dws, dbs, lossb = engine.alloc_grads(len(shapes), wp.shape[1], wp.shape[2])
+    outb = torch.empty(rows, n_out, dtype=torch.float32, device="cuda:0")
+    dT = torch.full((rows + 3, n_out), -7.25, dtype=torch.float32, device="cuda:0")
+    b = lnerf.LnerfBatch(rows, 1, lnerf.INPUT_ENCODED, 0, Xd.data_ptr(), None, Td.data_ptr(), 2.0, 6.0)
+    o = lnerf.LnerfOutputs(lossb.data_ptr(), outb.data_ptr(), dws.data_ptr(), dbs.data_ptr(), None, None, dT.data_ptr())
+    rc = engine.lib.lnerf_train_step(engine.ctx, ctypes.byref(mlp), wsd.data_ptr(), bsd.data_ptr(), ctypes.byref(b),
+                                     seed, lnerf.FAST | lnerf.HEAD_FIT, ctypes.byref(o), engine._stream())
+    assert rc == 0, lnerf.last_error()
+    torch.cuda.synchronize()
+    dT = dT.cpu().numpy()
+    assert (dT[rows:] == -7.25).all()
+    assert_close("d_target", dT[:rows], -2.0 * seed * (f64[1] - T), **TOL)
+    assert torch.equal(outb, out)
+
+
 def test_mlp_fit_sgd_loop_matches_oracle(engine, fit):
     """fit_img.py:423-532's inner loop on the device over 8 chunks of 256 rows (chunk_size^2): the
     gradient of chunk c seeded with the previous step's loss (c_float(0) before the first),

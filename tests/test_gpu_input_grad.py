@@ -207,6 +207,29 @@ def test_fused_step_input_gradient(engine, workloads, name, rays_mode, flags, se
     _assert_within(f"d_input {name} {'RAYS' if rays_mode else 'POINTS'} flags={flags} seed={seed}", got, want, bound)
 
 
+FREQ_WORKLOADS = (0, 10, 11, 20)    # k[0] = 3, 63 | 69, 123: both of k16's encoders, either side of 64
+
+
+@pytest.fixture(scope="module")
+def freq_workloads():
+    rays32, _ = _select_rays32(nerf_np.CONFIGS["cfg2"][0], 8)
+    return {F: (nerf_np.make_workload("cfg2", rays=8, num_functions=F), rays32) for F in FREQ_WORKLOADS}
+
+
+@pytest.mark.parametrize("flags", [0, 512, 4096])
+@pytest.mark.parametrize("rays_mode", [False, True])
+@pytest.mark.parametrize("F", FREQ_WORKLOADS)
+def test_fused_step_input_gradient_across_frequencies(engine, freq_workloads, F, rays_mode, flags):
+    """The step's own d_input (k16's d_x store into the scratch, k0 columns wide, then the encoding's
+    reverse) at F = 0, 10, 11 and 20 on 8 rays x 32 samples, seed = loss: the bound of
+    test_fused_step_input_gradient. The term of frequency 2^19 carries the weight 2^19 here."""
+    import lnerf
+    w, rays32 = freq_workloads[F]
+    got, want, bound, _ = _step_case(engine, w, rays_mode, lnerf.FAST | flags, None, rays32)
+    assert np.abs(want).max() > 0
+    _assert_within(f"d_input F={F} {'RAYS' if rays_mode else 'POINTS'} flags={flags}", got, want, bound)
+
+
 # ---- 5. the generic path ---------------------------------------------------------------------------
 
 GENERIC_TOL = dict(rtol=1e-4, atol_scale=1e-4)   # test_gpu_native.TOL, against the loma-order C oracle

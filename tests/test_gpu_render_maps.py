@@ -28,6 +28,7 @@ import pytest
 
 import nerf_np
 import render_maps_ref as ref
+import width_workloads as ww
 
 pytestmark = pytest.mark.gpu
 
@@ -292,6 +293,50 @@ def test_kr_rgba_matches_k16_bf16(engine):
     b, pb = run_maps(engine, inp, _flags()["k16_bf16"], want=("rgba",), target=False)
     assert pa["kr"] and not pb["kr"]
     np.testing.assert_allclose(a["rgba"], b["rgba"], rtol=2e-5, atol=2e-6 * max(1.0, np.abs(b["rgba"][:, 3]).max()))
+
+
+# ---- 3b. other first-layer widths and a wide head: the MAPS code objects ---------------------------
+
+WIDTH_PATHS = ("kr", "k16_bf16", "fp16x3", "bf16x6")
+
+
+@pytest.mark.parametrize("mode", ["rays", "points"])
+@pytest.mark.parametrize("path", WIDTH_PATHS)
+@pytest.mark.parametrize("F", [0, 10, 11])
+def test_same_picture_across_encoding_frequencies(engine, F, path, mode):
+    """The MAPS instantiations of kr and k16 are code objects of their own: k[0] = 3, 63 (k16's
+    recurrence encoder, kr) and 69 (the per-tile encoder, kr's fallback to k16) on 24 rays x 32
+    samples (tests/width_workloads.py). The colour and the loss are lnerf_render's bit for bit, the
+    path is the render's plus `maps`, and the fp32-class rgba is float64's."""
+    import lnerf
+    fl = _flags()[path]
+    w, rays6, X, dists = ww.case_workload(("freq", F, mode))
+    inp = _inputs(w, lnerf.INPUT_RAYS if mode == "rays" else lnerf.INPUT_POINTS, rays6)
+    loss, acc, rpath = run_render(engine, inp, fl)
+    out, mpath = run_maps(engine, inp, fl)
+    assert mpath == {**rpath, "maps": True}, (mpath, rpath)
+    assert mpath["kr"] == (path == "kr" and 3 + 6 * F <= 64) and mpath["k16"] and not mpath["generic"], mpath
+    assert mpath["planes"] == dict(kr=1, k16_bf16=1, fp16x3=2, bf16x6=3)[path]
+    assert np.array_equal(out["color"], acc)
+    assert out["loss"][0] == loss, (out["loss"][0], loss)
+    if path in ("fp16x3", "bf16x6"):
+        _assert_tol64(out["rgba"], _rgba64(X, w.ws, w.bs, dists, w.target, w.S))
+
+
+def test_head16_maps(engine):
+    """A 16-output head (columns 4.. eight times louder than 0..3): rgba is (rows, 4) of columns 0..3 --
+    float64's, with the rows past the end untouched (run_maps) -- and the picture is lnerf_render's."""
+    import lnerf
+    fl = _flags()["fp16x3"]
+    w, _, X, dists = ww.case_workload(("head", 16, "points"))
+    inp = _inputs(w, lnerf.INPUT_POINTS)
+    loss, acc, rpath = run_render(engine, inp, fl)
+    out, mpath = run_maps(engine, inp, fl)
+    assert mpath == {**rpath, "maps": True} and mpath["planes"] == 2, (mpath, rpath)
+    assert out["rgba"].shape == (w.N * w.S, 4)
+    assert np.array_equal(out["color"], acc) and out["loss"][0] == loss
+    _assert_tol64(out["rgba"], _rgba64(X, w.ws, w.bs, dists, w.target, w.S))
+    compositing_ratios(out, inp)
 
 
 # ---- 4. no target ----------------------------------------------------------------------------
