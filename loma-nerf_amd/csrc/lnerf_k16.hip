@@ -1083,6 +1083,16 @@ k16_fwd_bwd_kernel(K16Args a) {
                         act[q][o][i] = relu_bit(v, o >= 8 ? mhi : mlo);
                     }
                 }
+                // a layer-0 input wider than the hidden layers (k[0] > 16 HT) leaves its tiles past HT in
+                // act, which no later pass multiplies but every later sample_max would read as part of
+                // the row: the row shift (and the int24 slab's) would follow max|x| instead of the
+                // activations', and a row 2^-24 below its input keeps no bits (tests/test_gpu_scale.py)
+                if constexpr (HT < kMaxT) {
+                    if (l == 0) {
+#pragma unroll
+                        for (int o = HT; o < kMaxT; ++o) act[q][o] = fx4{0.0f, 0.0f, 0.0f, 0.0f};
+                    }
+                }
                 const unsigned long long mb = ((unsigned long long)mhi << 32) | mlo;
                 if (st) mask_w[q][(size_t)l * LW * 64] = mb;
             }

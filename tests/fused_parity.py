@@ -97,9 +97,12 @@ def run_fused(engine, w, *, points=True, seed=None, flags=0, want_dx=False, rays
 
 
 def check_fused(engine, w, *, points=True, seed=None, flags=0, want_dx=False, tol64=TOL64,
-                tolc=TOLC, c_oracle=True, rays32=None):
+                tolc=TOLC, c_oracle=True, rays32=None, per_layer=False):
     """rays32: INPUT_RAYS on these float32 rays; the references then take rays_reference's encoding
-    and dists in place of w's."""
+    and dists in place of w's. per_layer: besides the whole-tensor bars, dW per layer and per column
+    within 1e-5 |want| + 1e-4 x the column's max and dB per layer within 1e-5 |want| + 1e-4 x the
+    layer's max (scale_workloads.assert_per_layer), against float64; the worst ratios go into the
+    stats. Without it a layer 2^-40 below the loudest one is not checked at all."""
     import oracle
     got = run_fused(engine, w, points=points, seed=seed, flags=flags, want_dx=want_dx, rays32=rays32)
     X = encoded_input(w, points, rays32)
@@ -126,6 +129,10 @@ def check_fused(engine, w, *, points=True, seed=None, flags=0, want_dx=False, to
             worst = max(worst, float(mg.max()))
     assert worst <= FLIP_MARGIN, f"a ReLU decision differs from float64 at |z|/T = {worst:.3g}"
     stats = dict(rays=w.N, flips_vs_f64=flips, worst_flip_margin=worst)
+    if per_layer:
+        from scale_workloads import assert_per_layer
+        stats["dW_over_col_bar"], stats["dB_over_layer_bar"] = assert_per_layer(
+            got["dW"], got["dB"], ref["dW"], ref["db"], shapes)
     # 3. the loma-order fp32 oracle on the rays whose decisions agree with its own
     if c_oracle:
         want = oracle.standard_forward_backward(X, w.wp, w.bp, shapes, dists, w.target, w.S,
