@@ -56,3 +56,22 @@ def sums_from_weights(weights, rgb, t=None):
 def ray_t(S, near=2.0, far=6.0):
     """The depths RAYS mode samples at, as the engine rounds them: (float)linspace(near, far, S)."""
     return np.linspace(np.float32(near).astype(np.float64), np.float32(far).astype(np.float64), S).astype(np.float32)
+
+
+def map_ratios(out, dists, t, S):
+    """Per ray, the error of the maps in `out` (weights (N, S), opacity, depth (N), color (N, 3), rgba (N S, 4))
+    over the bars above, against float64 from the RETURNED rgba: what test_gpu_render_maps.compositing_ratios
+    asserts on the worst ray, kept per ray so that a sweep can report which rays fail. A sum of exact zeros
+    (a sigma = 0 ray) has a zero bar and must be exactly zero (inf otherwise)."""
+    N = np.asarray(dists).shape[0]
+    rgba = np.asarray(out["rgba"]).reshape(N, S, 4).astype(np.float64)
+    w64 = composite64(rgba[:, :, :3], rgba[:, :, 3], dists, t)
+    werr = np.abs(np.asarray(out["weights"], np.float64) - w64["weights"])
+    ratios = dict(weights=(werr / weights_bar(w64["weights"], S)).max(axis=1))
+    sums = sums_from_weights(out["weights"], rgba[:, :, :3], t)
+    for k in ("opacity", "depth", "color"):
+        s, bar = sums[k]
+        err = np.abs(np.asarray(out[k], np.float64) - s)
+        r = np.where(bar > 0, err / np.where(bar > 0, bar, 1.0), np.where(err > 0, np.inf, 0.0))
+        ratios[k] = r.reshape(N, -1).max(axis=1)
+    return ratios
