@@ -381,6 +381,49 @@ int lnerf_render_maps(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* ws, con
                       const lnerf_batch* batch, const float* sample_t, int flags,
                       const lnerf_render_outputs* out, void* stream);
 
+/* The reverse of lnerf_render_maps: the vector-Jacobian product of the render with the caller's
+ * adjoints of its maps, for any loss on colour, depth, opacity, sample weights and rgba (depth
+ * supervision, a mask loss, a white background C + (1 - O) bg, a regulariser on the weights, a robust
+ * colour loss, ...). An extension (the reference reverses its sum-of-squares colour loss only).
+ *   One call recomputes the forward exactly as lnerf_train_step does and reverses it from the
+ * adjoints. With t_j as in lnerf_render_maps, each sample's reverse is seeded with
+ *     dw_j     = rgb_j . d_acc_color + t_j d_depth + d_opacity + d_weights_j
+ *     drgb_j   = w_j d_acc_color + d_rgba_j[0..2]
+ *     dsigma_j += d_rgba_j[3]     (before the ReLU gate sigma > 0: rgba's sigma is the post-ReLU value)
+ * and everything after that -- the transmittance reverse, the alpha reverse, the head and the MLP's
+ * reverse chain, dW / db, the fp16x3 floor guard and its re-run, the exceptional rows -- is
+ * lnerf_train_step's. With d_acc_color = 2 (acc_color - target) and no other adjoint every output has
+ * lnerf_train_step's bits at LNERF_SEED_CONST, seed 1. A NULL adjoint's term is never formed (no
+ * 0 * x): a NaN or an infinity in t or rgb cannot leak through an adjoint that was not given, and the
+ * other terms keep their bits. All five NULL is an error. The seed is 1: the adjoints carry any scale.
+ *   Writes out->d_ws, d_bs, d_dists and, under LNERF_WANT_DX / LNERF_WANT_DINPUT, d_x (layouts and
+ * rules of lnerf_train_step), and out->acc_color, the recomputed colour (lnerf_train_step's bit for
+ * bit). batch->target is ignored and may be NULL; a non-NULL out->loss or out->d_target is an error.
+ * `out` and every output pointer may be NULL.
+ *   sample_t: NULL in RAYS mode (t_j = (float)linspace(near_t, far_t, S)[j]); in POINTS / ENCODED
+ * mode required with d_depth and not read otherwise. There is no gradient with respect to sample_t
+ * here: it is w_j d_depth per sample, which the caller forms from lnerf_render_maps' weights.
+ *   Flags: the default precision (fp16x3 with the floor guard), LNERF_MFMA_F16X3, LNERF_MFMA_BF16X6,
+ * LNERF_MFMA_BF16, LNERF_GENERIC, LNERF_FAST, LNERF_TIMING, LNERF_ACCUMULATE (fused path only),
+ * LNERF_WANT_DX, LNERF_WANT_DINPUT. LNERF_SEED_LOSS, LNERF_HEAD_FIT, LNERF_K16_W4 and
+ * LNERF_RENDER_K16 are errors. Shapes the fused path does not take (samples > 128, a head over 16
+ * outputs) run the generic path, which has no limit on samples. An error launches nothing and writes
+ * nothing. Afterwards lnerf_ctx_relu_masks, _exceptional_rows, _guard_fired, _timings and
+ * _workspace_used behave as after a training step, and lnerf_ctx_last_path reports the training
+ * step's bits plus LNERF_PATH_VJP. */
+typedef struct {               /* device pointers, each nullable; all NULL is an error */
+    const float* d_acc_color;  /* (rays, 3)    */
+    const float* d_depth;      /* (rays)       */
+    const float* d_opacity;    /* (rays)       */
+    const float* d_weights;    /* (rays, S)    */
+    const float* d_rgba;       /* (rays*S, 4), 16-byte aligned */
+} lnerf_render_adjoints;
+
+int lnerf_render_maps_vjp(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* ws, const float* bs,
+                          const lnerf_batch* batch, const float* sample_t,
+                          const lnerf_render_adjoints* adj, int flags, const lnerf_outputs* out,
+                          void* stream);
+
 /* Per-kernel times (ms) of the last LNERF_TIMING step or render on `ctx`, measured with HIP events
  * on its stream: [0] weight pack, [1] fused fwd+reverse-chain kernel (a render: the forward
  * kernel), [2] loss reduce, [3] dW kernel, [4] dW/db reduce (with LNERF_WANT_DINPUT also the
@@ -402,7 +445,8 @@ enum {
     LNERF_PATH_K16_W4 = 32,   /* k16 on 4-wave, 64-sample workgroups (two per CU)             */
     LNERF_PATH_KR = 64,       /* the render ran kr (lnerf_render.hip), not k16's forward      */
     LNERF_PATH_A24 = 128,     /* training kept the activation slabs as int24 (fp16x3)         */
-    LNERF_PATH_MAPS = 1024    /* lnerf_render_maps: the MAPS instantiations (bits 8-9: planes)  */
+    LNERF_PATH_MAPS = 1024,   /* lnerf_render_maps: the MAPS instantiations (bits 8-9: planes)  */
+    LNERF_PATH_VJP = 2048     /* lnerf_render_maps_vjp: the training step's bits plus this one  */
 };
 int lnerf_ctx_last_path(lnerf_ctx* ctx);
 

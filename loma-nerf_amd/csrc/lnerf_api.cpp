@@ -575,7 +575,8 @@ extern "C" size_t lnerf_workspace_bytes(const lnerf_mlp* mlp, int rays, int samp
 // fresh zero arrays for every call, :313-317, :370-392).
 static void generic_step(lnerf_ctx* ctx, const lnerf_mlp& m, const float* ws, const float* bs,
                          const lnerf_batch& bt, float seed, int flags, const lnerf_outputs& out,
-                         bool want_grad, hipStream_t s, const comp::MapsArgs* maps = nullptr) {
+                         bool want_grad, hipStream_t s, const comp::MapsArgs* maps = nullptr,
+                         const comp::VjpArgs* vjp = nullptr) {
     const int L = m.num_layers, R = bt.rays * bt.samples, S = bt.samples, th = bt.rays;
     if (want_grad && (flags & LNERF_ACCUMULATE))
         fail("LNERF_ACCUMULATE is only supported on the fused path");
@@ -632,7 +633,7 @@ static void generic_step(lnerf_ctx* ctx, const lnerf_mlp& m, const float* ws, co
     b.X = X;
     b.W = ws;
     b.B = bs;
-    b.T = bt.target;
+    b.T = vjp ? nullptr : bt.target;   // lnerf_render_maps_vjp ignores the target: no loss stage
     b.IO = g + oIO;
     b.rgba = g + org;
     b.dists = dists;
@@ -675,7 +676,9 @@ static void generic_step(lnerf_ctx* ctx, const lnerf_mlp& m, const float* ws, co
     a.dcp = g + odcp;
     a.dwsamp = g + odws;
     a.dacc = g + odacc;
-    lg_nerf_grad(d, b, a, seed_dev, s);
+    // lnerf_render_maps_vjp: the compositing reverse seeded from the caller's adjoints
+    const LgVjp lv{vjp ? *vjp : comp::VjpArgs{}, bt.input_mode == LNERF_INPUT_RAYS, bt.near_t, bt.far_t};
+    lg_nerf_grad(d, b, a, seed_dev, s, vjp ? &lv : nullptr);
     const size_t nW = (size_t)L * m.w_k * m.w_n, nB = (size_t)L * m.w_n;
     auto emit = [&](float* dst, const float* src, size_t n) {
         if (dst) HIP_OK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -976,6 +979,91 @@ extern "C" int lnerf_render_maps(lnerf_ctx* ctx, const lnerf_mlp* mlp, const flo
             ctx->last_path = LNERF_PATH_GENERIC | LNERF_PATH_MAPS;
         }
         check_launch("lnerf_render_maps");
+    });
+}
+
+extern "C" int lnerf_render_maps_vjp(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* ws, const float* bs,
+                                     const lnerf_batch* batch, const float* sample_t,
+                                     const lnerf_render_adjoints* adj, int flags, const lnerf_outputs* out,
+                                     void* stream) {
+    return guard_int([&]() {
+        if (!ctx) fail("null ctx");
+        constexpr int kRefused = LNERF_SEED_LOSS | LNERF_HEAD_FIT | LNERF_K16_W4 | LNERF_RENDER_K16;
+        if (flags & kRefused)
+            fail("lnerf_render_maps_vjp: flags 0x%x (LNERF_SEED_LOSS / LNERF_HEAD_FIT / LNERF_K16_W4 / "
+                 "LNERF_RENDER_K16) have no meaning here", flags & kRefused);
+        validate(mlp, batch, false);
+        validate_head(mlp, batch, flags);
+        if (!ws || !bs) fail("null weights");
+        if (!adj) fail("lnerf_render_maps_vjp: null adjoints");
+        const comp::VjpArgs vjp{adj->d_acc_color, adj->d_depth, adj->d_opacity, adj->d_weights, adj->d_rgba, sample_t};
+        if (!vjp.d_acc_color && !vjp.d_depth && !vjp.d_opacity && !vjp.d_weights && !vjp.d_rgba)
+            fail("lnerf_render_maps_vjp: every adjoint is NULL (nothing to reverse)");
+        if ((uintptr_t)vjp.d_rgba % 16) fail("lnerf_render_maps_vjp: adj->d_rgba must be 16-byte aligned (one load per sample)");
+        if (batch->input_mode == LNERF_INPUT_RAYS) {
+            if (sample_t) fail("lnerf_render_maps_vjp: sample_t must be NULL in RAYS mode (the engine samples the depths)");
+        } else if (vjp.d_depth && !sample_t) {
+            fail("lnerf_render_maps_vjp: d_depth needs sample_t (rays, S) in POINTS / ENCODED mode");
+        }
+        lnerf_outputs o = out ? *out : lnerf_outputs{};
+        if (o.loss || o.d_target)
+            fail("lnerf_render_maps_vjp: out->loss and out->d_target must be NULL (there is no loss and no target)");
+        // d_x as lnerf_train_step forms it (LNERF_WANT_DX / LNERF_WANT_DINPUT)
+        if (flags & LNERF_WANT_DINPUT) {
+            if (batch->input_mode == LNERF_INPUT_ENCODED) flags |= LNERF_WANT_DX;
+            else if (flags & LNERF_WANT_DX)
+                fail("LNERF_WANT_DX | LNERF_WANT_DINPUT needs ENCODED input (d_x cannot hold both layouts)");
+            else if (batch->num_freqs > kMaxInputGradFreqs)
+                fail("LNERF_WANT_DINPUT runs at most %d frequencies", kMaxInputGradFreqs);
+        }
+        if (!(flags & (LNERF_WANT_DX | LNERF_WANT_DINPUT))) o.d_x = nullptr;
+        float* d_input = (flags & LNERF_WANT_DX) ? nullptr : o.d_x;   // non-null: reverse the encoding
+        check_precision_flags(flags);
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        ctx->last_k16_train = false;
+        HIP_OK(hipSetDevice(ctx->device));
+        hipStream_t s = (hipStream_t)stream;   // NULL: the device's default (null) stream
+        const bool fused = use_fused(*mlp, *batch, flags);
+        if (!fused && (flags & LNERF_ACCUMULATE)) fail("LNERF_ACCUMULATE is only supported on the fused path");
+        if (d_input)
+            o.d_x = (float*)ctx->dinput_ws.get((size_t)batch->rays * batch->samples * mlp->k[0] * sizeof(float));
+        if (fused) {
+            const size_t bytes = fused_workspace_bytes(*mlp, batch->rays, batch->samples, true, ctx->dw_grid);
+            FusedPlan p{};
+            void* wsb = ctx->fused_ws.get(bytes);
+            fused_plan(p, *mlp, *batch, wsb, flags, true, ctx->dw_grid);
+            ctx->ws_used = 0;
+            // the fp16x3 floor guard under the default precision, as in lnerf_train_step
+            const bool guarded = LNERF_GUARD && p.x6 == 2 && !(flags & LNERF_MFMA_F16X3);
+            FusedPlan px{};
+            if (guarded) {
+                fused_plan(px, *mlp, *batch, wsb, flags | LNERF_MFMA_BF16X6, true, ctx->dw_grid);
+                px.guard = nullptr;
+                px.gate = p.guard;
+                px.w16 = p.w16x;
+                px.w16x = nullptr;
+                ctx->ws_used = check_workspace(px, bytes);
+            } else {
+                ctx->ws_used = check_workspace(p, bytes);
+                p.guard = nullptr;
+                p.w16x = nullptr;
+            }
+            const bool timed = (flags & LNERF_TIMING) != 0;
+            fused_render_vjp(p, ws, bs, *batch, flags, o, vjp, s, timed ? ctx->ev : nullptr, guarded ? &px : nullptr,
+                             d_input);
+            check_launch("lnerf_render_maps_vjp");
+            ctx->timed = timed;
+            ctx->last_path = path_bits(p, true) | LNERF_PATH_VJP;
+            ctx->last_plan = p;
+            ctx->last_k16_train = true;
+        } else {
+            ctx->ws_used = 0;
+            generic_step(ctx, *mlp, ws, bs, *batch, 1.0f, flags, o, true, s, nullptr, &vjp);
+            if (d_input) k_input_grad(*batch, o.d_x, nullptr, d_input, s);
+            ctx->timed = false;
+            ctx->last_path = LNERF_PATH_GENERIC | LNERF_PATH_VJP;
+        }
+        check_launch("lnerf_render_maps_vjp");
     });
 }
 

@@ -421,6 +421,38 @@ void fused_train_step(const FusedPlan& p, const float* ws, const float* bs, cons
     mark(5);
 }
 
+// lnerf_render_maps_vjp: fused_train_step's sequence on the VJP instantiations of k1, seeded from the
+// caller's adjoints (seed 1, no loss: k1 leaves loss_part 0, and k1_reduce's launch is kept for the dW
+// product shifts it also forms).
+void fused_render_vjp(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b, int flags,
+                      const lnerf_outputs& out, const comp::VjpArgs& vjp, hipStream_t s, hipEvent_t* ev,
+                      const FusedPlan* px, float* d_input) {
+    auto mark = [&](int i) {
+        if (ev) (void)hipEventRecord(ev[i], s);
+    };
+    const size_t nred = (size_t)p.L * p.w_k * p.w_n + (size_t)p.L * p.w_n;
+    const unsigned rgrid = (unsigned)((nred + 255) / 256);
+    mark(0);
+    k16_pack(p, ws, bs, s);
+    mark(1);
+    k16_launch_vjp(p, b, out, vjp, s);
+    mark(2);
+    k1_reduce_launch(p, nullptr, s);
+    mark(3);
+    dw16_launch(p, s);
+    mark(4);
+    if (px && p.guard) {
+        // the floor guard's re-run on the bf16x6 split, gated on the device as in fused_train_step
+        k16_launch_vjp(*px, b, out, vjp, s);
+        k1_reduce_launch(*px, nullptr, s);
+        dw16_launch(*px, s);
+    }
+    const ReduceArgs ra = reduce_args(p, out, flags & LNERF_ACCUMULATE);
+    grad_reduce_kernel<<<rgrid, 256, 0, s>>>(ra);
+    if (d_input && out.d_x) k_input_grad(b, out.d_x, nullptr, d_input, s);
+    mark(5);
+}
+
 // Plain bf16 (config 5's inference precision) runs kr (lnerf_render.hip: every weight fragment
 // feeds two 16-sample groups) unless LNERF_RENDER_K16 asks for k16's forward; the split
 // precisions run k16's forward. Both read k16_pack's planes.

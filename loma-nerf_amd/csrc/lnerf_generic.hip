@@ -474,14 +474,17 @@ void k_ray_maps(const float* wsamp, const float* sample_t, int rays, int S, floa
 }
 
 void lg_nerf_grad(const LgDims& d, const LgBuffers& b, const LgAdjoints& a, const float* seed_dev,
-                  hipStream_t s) {
+                  hipStream_t s, const LgVjp* vjp) {
     // re-execute the forward on the private primal copy, with snapshots
     mlp_forward(d, b, s);
     if (d.th > 0) {
         lg_composite_fwd_kernel<<<(d.th + 127) / 128, 128, 0, s>>>(
             d, b.IO, b.rgba, b.dists, b.alpha, b.cp, b.wsamp, b.acc, b.cpC, b.cpP);
-        lg_composite_bwd_kernel<<<(d.th + 127) / 128, 128, 0, s>>>(
-            d, b.T, b.acc, b.rgba, b.dists, b.alpha, b.cp, b.cpC, b.cpP, b.wsamp, a, seed_dev);
+        if (vjp)
+            lg_composite_vjp_launch(d, b, a, *vjp, s);
+        else
+            lg_composite_bwd_kernel<<<(d.th + 127) / 128, 128, 0, s>>>(
+                d, b.T, b.acc, b.rgba, b.dists, b.alpha, b.cp, b.cpC, b.cpP, b.wsamp, a, seed_dev);
     }
     mlp_reverse(d, b, a, s);
 }

@@ -182,8 +182,11 @@ void lg_nerf_forward(const LgDims& d, const LgBuffers& b, float* loss_dev, hipSt
 // grad_nerf_evaluate_and_march: b must hold a *fresh copy* of the primal inputs (the forward is
 // re-executed on it, snapshots filled); adjoints accumulate in `a`. `seed_dev` is a device
 // scalar (so the seed may be a loss computed on the device).
+// vjp (nullable; lnerf_render_maps_vjp): the compositing reverse is seeded from the caller's adjoints
+// (lg_composite_vjp_launch) instead of the loss; b.T and seed_dev are not read then.
+struct LgVjp;
 void lg_nerf_grad(const LgDims& d, const LgBuffers& b, const LgAdjoints& a, const float* seed_dev,
-                  hipStream_t s);
+                  hipStream_t s, const LgVjp* vjp = nullptr);
 void lg_mlp_fit_forward(const LgDims& d, const LgBuffers& b, float* loss_dev, hipStream_t s);
 void lg_mlp_fit_grad(const LgDims& d, const LgBuffers& b, const LgAdjoints& a,
                      const float* seed_dev, hipStream_t s);
@@ -369,5 +372,42 @@ void kr_launch_maps(const FusedPlan& p, const lnerf_batch& b, const lnerf_output
 // opacity nullable.
 void k_ray_maps(const float* wsamp, const float* sample_t, int rays, int S, float near_t, float far_t,
                 float* depth, float* opacity, hipStream_t s);
+
+// ---- render maps, reverse (lnerf_render_maps_vjp) -----------------------------------------------
+namespace comp {
+// The caller's adjoints of the render maps (an extension, as the maps themselves): what the VJP
+// compositing (composite_tile_wave_vjp, lg_composite_vjp_kernel) seeds the reverse pass with instead
+// of the loss's dacc = 2 seed (C - target):
+//   dw_j     = rgb_j . dC + t_j dD + dO + dWt_j
+//   drgb_j   = w_j dC + dRGBA_j[0..2]
+//   dsigma_j += dRGBA_j[3]   (before the ReLU gate sigma > 0: rgba's sigma is the post-ReLU value)
+// Every pointer is nullable; a NULL adjoint's term is never formed (no 0 * x). sample_t (POINTS /
+// ENCODED input) is read only with d_depth; RAYS input takes t_j = (float)ray_depth(j, S, near_t, far_t).
+struct VjpArgs {
+    const float* d_acc_color;  // (rays, 3)
+    const float* d_depth;      // (rays)
+    const float* d_opacity;    // (rays)
+    const float* d_weights;    // (rays, S)
+    const float* d_rgba;       // (rays*S, 4), 16-byte aligned
+    const float* sample_t;     // (rays, S) or NULL
+};
+}  // namespace comp
+// fused_train_step's sequence on the VJP instantiations of k1 (lnerf_k16_vjp.hip): pack, k1, the dW
+// product shifts, dW, the gated bf16x6 re-run (px), the dW/db reduce and the optional input gradient
+// (d_input). No loss is formed or reduced; the adjoints carry any scale (the seed is 1).
+void fused_render_vjp(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b, int flags,
+                      const lnerf_outputs& out, const comp::VjpArgs& vjp, hipStream_t s, hipEvent_t* ev,
+                      const FusedPlan* px = nullptr, float* d_input = nullptr);
+void k16_launch_vjp(const FusedPlan& p, const lnerf_batch& b, const lnerf_outputs& out, const comp::VjpArgs& vjp,
+                    hipStream_t s);
+// generic path (lnerf_generic_vjp.hip): lg_composite_bwd_kernel's stages seeded from the adjoints
+// instead of the loss; t_j = vjp.sample_t, or ray_depth(j) when rays_mode
+struct LgVjp {
+    comp::VjpArgs v;
+    int rays_mode;
+    float near_t, far_t;
+};
+void lg_composite_vjp_launch(const LgDims& d, const LgBuffers& b, const LgAdjoints& a, const LgVjp& vjp,
+                             hipStream_t s);
 
 }  // namespace lnerf

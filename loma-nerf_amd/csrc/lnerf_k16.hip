@@ -34,6 +34,16 @@
 #ifndef LNERF_MAPS_TU
 #define LNERF_MAPS_TU 0
 #endif
+// LNERF_VJP_TU: lnerf_k16_vjp.hip compiles this file once more for the VJP instantiations alone
+// (lnerf_render_maps_vjp: k16_launch_vjp), for the same reason.
+#ifndef LNERF_VJP_TU
+#define LNERF_VJP_TU 0
+#endif
+#if LNERF_VJP_TU
+#include "lnerf_composite_vjp.h"
+#endif
+// the plain object: training, lnerf_render, the packing, the mask readback and the knobs
+#define LNERF_PLAIN_TU (!LNERF_MAPS_TU && !LNERF_VJP_TU)
 
 namespace lnerf {
 
@@ -131,6 +141,9 @@ struct K16Args {
 #if LNERF_MAPS_TU
     comp::MapsArgs maps;   // the render maps (the MAPS object only: the plain object's kernel-argument
                            // segment keeps its size, which the kernels' code refers to)
+#endif
+#if LNERF_VJP_TU
+    comp::VjpArgs vjp;     // the caller's adjoints of the render maps (the VJP object only, as above)
 #endif
 };
 
@@ -932,7 +945,14 @@ __device__ __forceinline__ void zero_tiles(fx4 (&t)[kMaxT]) {
 // MAPS (lnerf_render_maps, launched forward-only): the compositing also writes the render maps a.maps
 // and takes a NULL target. The rest of the kernel, the reverse chain included, is the same source: every
 // kernel of this name carries the slab stores tests/test_isa.py audits.
+// VJP (lnerf_render_maps_vjp, launched with gradients; a template parameter of the VJP object only, so
+// the other objects' kernels keep their names): the compositing seeds the reverse from the adjoints
+// a.vjp instead of the loss (comp::composite_tile_wave_vjp); loss_part comes out 0.
+#if LNERF_VJP_TU
+template <int HT, int PL, int NW, int NG = 1, bool MAPS = false, bool VJP = false>
+#else
 template <int HT, int PL, int NW, int NG = 1, bool MAPS = false>
+#endif
 __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NG == 2 ? 1 : 2, NG == 2 ? 1 : 2)))
 k16_fwd_bwd_kernel(K16Args a) {
     using R = Ring<PL, NW, NG>;
@@ -1118,6 +1138,10 @@ k16_fwd_bwd_kernel(K16Args a) {
     __syncthreads();
 
     // ---- rendering + loss + rendering reverse (one thread per sample, scans along rays) ----
+#if LNERF_VJP_TU
+    if constexpr (VJP) comp::composite_tile_wave_vjp<comp::kTileSamples>(a, wg, comp, rayloss, a.vjp);
+    else
+#endif
     if (a.head_fit) comp::fit_tile(a, wg, comp, rayloss, st, a.nout);
 #if LNERF_MAPS_TU
     else if constexpr (MAPS) comp::composite_tile_wave<comp::kTileSamples, true>(a, wg, comp, rayloss, false, a.maps);
@@ -1262,7 +1286,7 @@ k16_fwd_bwd_kernel(K16Args a) {
 #endif
 }
 
-#if !LNERF_MAPS_TU   // (the packing, the mask readback and the knobs belong to the plain object)
+#if LNERF_PLAIN_TU   // (the packing, the mask readback and the knobs belong to the plain object)
 // ---- weight packing: per layer and pass, chunk s = [o][plane][lane 64][8 x bf16] -----------
 // forward:  A[m = out 16o + (lane & 15)][k = 8g + j] = W[phi(s, g, j)][16o + m]
 // backward: A[m = in  16o + (lane & 15)][k = 8g + j] = W[16o + m][phi(s, g, j)]
@@ -1409,11 +1433,11 @@ __global__ void k16_masks_kernel(const unsigned long long* __restrict__ mask_g, 
     out[idx] = (unsigned char)(lo | (hi << 4));
 }
 
-#endif   // !LNERF_MAPS_TU
+#endif   // LNERF_PLAIN_TU
 
 }  // namespace
 
-#if !LNERF_MAPS_TU
+#if LNERF_PLAIN_TU
 // Compile-time settings of this object that differ from the product build (lnerf_build_knobs):
 // 0 for the shipped library; an A/B variant built with -D... reports which knob it moved.
 unsigned k16_build_knobs() {
@@ -1476,6 +1500,13 @@ void k16_pack(const FusedPlan& p, const float* ws, const float* bs, hipStream_t 
 
 void k16_launch(const FusedPlan& p, const lnerf_batch& b, float seed, const lnerf_outputs& out,
                 bool want_grad, hipStream_t s) {
+#elif LNERF_VJP_TU
+// k16's forward and reverse chain with the VJP compositing (lnerf_render_maps_vjp): the same launch as
+// k16_launch with gradients at seed 1 and no target, on the VJP instantiations (8-wave workgroups)
+void k16_launch_vjp(const FusedPlan& p, const lnerf_batch& b, const lnerf_outputs& out, const comp::VjpArgs& vjp,
+                    hipStream_t s) {
+    const float seed = 1.0f;
+    const bool want_grad = true;
 #else
 // k16's forward with the MAPS compositing (lnerf_render_maps): the same launch as k16_launch without
 // gradients, on the MAPS instantiations
@@ -1484,10 +1515,13 @@ void k16_launch_maps(const FusedPlan& p, const lnerf_batch& b, const lnerf_outpu
     const float seed = 1.0f;
     const bool want_grad = false;
 #endif
-    constexpr bool kMaps = LNERF_MAPS_TU != 0;
+    [[maybe_unused]] constexpr bool kMaps = LNERF_MAPS_TU != 0;
     K16Args a{};
 #if LNERF_MAPS_TU
     a.maps = maps;
+#endif
+#if LNERF_VJP_TU
+    a.vjp = vjp;
 #endif
     a.L = p.L;
     for (int l = 0; l < p.L; ++l) {
@@ -1519,11 +1553,11 @@ void k16_launch_maps(const FusedPlan& p, const lnerf_batch& b, const lnerf_outpu
     a.far_t = b.far_t;
     a.x = b.x;
     a.dists = b.input_mode == LNERF_INPUT_RAYS ? nullptr : b.dists;
-    a.target = b.target;
+    a.target = LNERF_VJP_TU ? nullptr : b.target;
     a.loss_part = p.loss_part;
     a.acc_color = out.acc_color;
     a.d_dists = want_grad ? out.d_dists : nullptr;
-    a.d_target = want_grad ? out.d_target : nullptr;
+    a.d_target = want_grad && !LNERF_VJP_TU ? out.d_target : nullptr;
     a.d_x = want_grad ? out.d_x : nullptr;
     a.seed = seed;
     a.want_grad = want_grad ? 1 : 0;
@@ -1558,18 +1592,25 @@ void k16_launch_maps(const FusedPlan& p, const lnerf_batch& b, const lnerf_outpu
         // a zero entry past the end (the kernel looks one chunk ahead): a{} zeroed it
     }
     static_assert(sizeof(K16Args) <= 4096, "kernel arguments");
-#if LNERF_K16_G2 && !LNERF_MAPS_TU
+#if LNERF_K16_G2 && LNERF_PLAIN_TU
     // two 16-sample groups per wave, one wave per SIMD (fp16x3, 256-wide hidden layers, 128-sample tiles)
     if (p.x6 == 2 && p.tile == 128 && p.ht16 == 16) {
         k16_fwd_bwd_kernel<16, 2, 4, 2><<<p.num_wg, 256, 0, s>>>(a);
         return;
     }
 #endif
-#if defined(LNERF_K16_ONLY_16_2) && !LNERF_MAPS_TU   // compile-time experiments: one instantiation
+#if defined(LNERF_K16_ONLY_16_2) && LNERF_PLAIN_TU   // compile-time experiments: one instantiation
     if (p.tile == 64) k16_fwd_bwd_kernel<16, 2, 4><<<p.num_wg, 256, 0, s>>>(a);
     else k16_fwd_bwd_kernel<16, 2, 8><<<p.num_wg, 512, 0, s>>>(a);
     return;
 #endif
+#if LNERF_VJP_TU
+// (lnerf_render_maps_vjp refuses LNERF_K16_W4: every plan has 128-sample tiles)
+#define LNERF_K16_LAUNCH(HT)                                                                 \
+    if (p.x6 == 3) k16_fwd_bwd_kernel<HT, 3, 8, 1, false, true><<<p.num_wg, 512, 0, s>>>(a);           \
+    else if (p.x6 == 2) k16_fwd_bwd_kernel<HT, 2, 8, 1, false, true><<<p.num_wg, 512, 0, s>>>(a);      \
+    else k16_fwd_bwd_kernel<HT, 1, 8, 1, false, true><<<p.num_wg, 512, 0, s>>>(a);
+#else
 // bf16x6 (three planes) always runs the 8-wave workgroup (its ring does not fit two per CU)
 #define LNERF_K16_LAUNCH(HT)                                                                 \
     if (p.x6 == 3) k16_fwd_bwd_kernel<HT, 3, 8, 1, kMaps><<<p.num_wg, 512, 0, s>>>(a);                 \
@@ -1577,6 +1618,7 @@ void k16_launch_maps(const FusedPlan& p, const lnerf_batch& b, const lnerf_outpu
     else if (p.tile == 64) k16_fwd_bwd_kernel<HT, 1, 4, 1, kMaps><<<p.num_wg, 256, 0, s>>>(a);         \
     else if (p.x6 == 2) k16_fwd_bwd_kernel<HT, 2, 8, 1, kMaps><<<p.num_wg, 512, 0, s>>>(a);            \
     else k16_fwd_bwd_kernel<HT, 1, 8, 1, kMaps><<<p.num_wg, 512, 0, s>>>(a);
+#endif
     switch (p.ht16) {
         case 1: LNERF_K16_LAUNCH(1) break;
         case 2: LNERF_K16_LAUNCH(2) break;

@@ -50,7 +50,7 @@ EXPORTED_SYMBOLS = [
     "lnerf_ctx_set_option", "lnerf_ctx_relu_masks", "lnerf_build_knobs", "lnerf_ctx_exceptional_rows",
     "lnerf_ctx_guard_fired", "lnerf_input_grad", "lnerf_pose_grad", "lnerf_ctx_workspace_used",
     "lnerf_render_maps", "lnerf_sample_stratified", "lnerf_sample_importance", "lnerf_ray_points",
-    "lnerf_ray_points_grad",
+    "lnerf_ray_points_grad", "lnerf_render_maps_vjp",
 ]
 
 # lnerf_ctx_last_path bits
@@ -63,6 +63,7 @@ PATH_K16_W4 = 32
 PATH_KR = 64       # the render ran kr (lnerf_render.hip)
 PATH_A24 = 128      # training kept the activation slabs as int24 (fp16x3)
 PATH_MAPS = 1024    # lnerf_render_maps: the MAPS instantiations (bits 8-9 hold the plane count)
+PATH_VJP = 2048     # lnerf_render_maps_vjp: the training step's bits plus this one
 
 
 class LnerfMLP(ctypes.Structure):
@@ -85,6 +86,11 @@ class LnerfOutputs(ctypes.Structure):
 class LnerfRenderOutputs(ctypes.Structure):
     _fields_ = [("acc_color", ctypes.c_void_p), ("depth", ctypes.c_void_p), ("opacity", ctypes.c_void_p),
                 ("weights", ctypes.c_void_p), ("rgba", ctypes.c_void_p), ("loss", ctypes.c_void_p)]
+
+
+class LnerfRenderAdjoints(ctypes.Structure):
+    _fields_ = [("d_acc_color", ctypes.c_void_p), ("d_depth", ctypes.c_void_p), ("d_opacity", ctypes.c_void_p),
+                ("d_weights", ctypes.c_void_p), ("d_rgba", ctypes.c_void_p)]
 
 
 _LIB = None
@@ -197,6 +203,12 @@ def configure(lib: ctypes.CDLL) -> None:
                                           ctypes.c_void_p, ctypes.POINTER(LnerfBatch), ctypes.c_void_p,
                                           ctypes.c_int, ctypes.POINTER(LnerfRenderOutputs), ctypes.c_void_p]
         lib.lnerf_render_maps.restype = ctypes.c_int
+    if hasattr(lib, "lnerf_render_maps_vjp"):   # (older in-tree A/B builds lack the render's reverse)
+        lib.lnerf_render_maps_vjp.argtypes = [ctypes.c_void_p, ctypes.POINTER(LnerfMLP), ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.POINTER(LnerfBatch), ctypes.c_void_p,
+                                              ctypes.POINTER(LnerfRenderAdjoints), ctypes.c_int,
+                                              ctypes.POINTER(LnerfOutputs), ctypes.c_void_p]
+        lib.lnerf_render_maps_vjp.restype = ctypes.c_int
     if hasattr(lib, "lnerf_sample_importance"):   # (older in-tree A/B builds lack the sampling kernels)
         vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
         lib.lnerf_sample_stratified.argtypes = [ci, ci, cf, cf, vp, vp, vp]
@@ -261,6 +273,19 @@ class RenderMaps:
 
 
 MAP_NAMES = ("color", "depth", "opacity", "weights", "rgba", "loss")
+ADJOINT_NAMES = ("color", "depth", "opacity", "weights", "rgba")   # the maps render_maps_vjp reverses
+
+
+@dataclass
+class VjpResult:
+    """Engine.render_maps_vjp's result: device tensors, None where not asked for."""
+    acc_color: object        # (rays, 3), the recomputed colour (train_step's bits)
+    grads: object            # packed [d_ws (L*w_k*w_n), d_bs (L*w_n), unused] (device)
+    d_ws: object
+    d_bs: object
+    d_dists: object = None   # (rays, S)
+    d_x: object = None       # want_dx: (rays*S, k[0])
+    d_input: object = None   # want_dinput: the gradient with respect to x, in x's shape
 
 
 class Engine:
@@ -417,6 +442,54 @@ class Engine:
         if "loss" in bufs:
             bufs["loss"] = bufs["loss"][0]
         return RenderMaps(**bufs)
+
+    def render_maps_vjp(self, mlp: LnerfMLP, ws, bs, x, dists, adjoints: dict, *, samples: int,
+                        input_mode: int = INPUT_POINTS, num_freqs: int = 5, near: float = 2.0,
+                        far: float = 6.0, sample_t=None, flags: int = 0, grads=None,
+                        want_dists: bool = True, want_dx: bool = False, want_dinput: bool = False,
+                        acc_color=None) -> VjpResult:
+        """lnerf_render_maps_vjp: the reverse of render_maps. `adjoints` maps names of ADJOINT_NAMES to
+        the float32 device tensors dL/d(map) -- color (rays, 3), depth (rays), opacity (rays), weights
+        (rays, S), rgba (rays*S, 4); a missing or None entry contributes nothing, at least one is
+        needed. One call recomputes the forward and returns the gradients with respect to ws, bs,
+        dists and (want_dx / want_dinput, as train_step) x; the adjoints carry any loss scale.
+        INPUT_POINTS / INPUT_ENCODED: sample_t (rays, S) is required with a depth adjoint. The
+        gradient with respect to sample_t is weights * d_depth[:, None], a torch op on render_maps'
+        weights. `grads` (from alloc_grads) is reused if given, and added into under ACCUMULATE."""
+        torch = self.torch
+        unknown = set(adjoints) - set(ADJOINT_NAMES)
+        if unknown:
+            raise ValueError(f"unknown adjoints {sorted(unknown)} (known: {ADJOINT_NAMES})")
+        rays = x.shape[0] if input_mode == INPUT_RAYS else x.shape[0] // samples
+        shapes = dict(color=(rays, 3), depth=(rays,), opacity=(rays,), weights=(rays, samples),
+                      rgba=(rays * samples, 4))
+        adj = {k: self._f32(f"adjoints[{k!r}]", v, shapes[k]) for k, v in adjoints.items() if v is not None}
+        b = LnerfBatch(rays, samples, input_mode, num_freqs, x.data_ptr(),
+                       None if dists is None else dists.data_ptr(), None, float(near), float(far))
+        if grads is None:
+            grads = self.alloc_grads(mlp.num_layers, mlp.w_k, mlp.w_n)
+        g, dws, dbs, _ = grads
+        if acc_color is None:
+            acc_color = torch.empty(rays, 3, dtype=torch.float32, device=x.device)
+        d_dists = torch.empty(rays, samples, dtype=torch.float32, device=x.device) if want_dists else None
+        d_x = None
+        if want_dx:
+            d_x = torch.zeros(rays * samples, mlp.k[0], dtype=torch.float32, device=x.device)
+            flags |= WANT_DX
+        d_input = None
+        if want_dinput:
+            d_input = d_x if d_x is not None else torch.zeros_like(x, dtype=torch.float32)
+            d_x = d_input
+            flags |= WANT_DINPUT
+        a = LnerfRenderAdjoints(_ptr(adj.get("color")), _ptr(adj.get("depth")), _ptr(adj.get("opacity")),
+                                _ptr(adj.get("weights")), _ptr(adj.get("rgba")))
+        o = LnerfOutputs(None, acc_color.data_ptr(), dws.data_ptr(), dbs.data_ptr(), _ptr(d_x), _ptr(d_dists), None)
+        rc = self.lib.lnerf_render_maps_vjp(self.ctx, ctypes.byref(mlp), ws.data_ptr(), bs.data_ptr(),
+                                            ctypes.byref(b), _ptr(sample_t), ctypes.byref(a), flags,
+                                            ctypes.byref(o), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_render_maps_vjp: {last_error()}")
+        return VjpResult(acc_color, g, dws, dbs, d_dists, d_x if want_dx else None, d_input)
 
     def get_rays(self, width: int, K, c2w):
         """train_nerf.py:23-62 on the device: (width*width, 6) float32 rays [o, d]."""
@@ -602,6 +675,8 @@ class Engine:
                  planes=(v >> 8) & 3)
         if v & PATH_MAPS:   # only after render_maps: the kernels' bits as after render, plus this key
             d["maps"] = True
+        if v & PATH_VJP:    # only after render_maps_vjp: the training step's bits, plus this key
+            d["vjp"] = True
         return d
 
     def relu_masks(self, L: int, R: int):
@@ -636,3 +711,79 @@ class Engine:
                                         self._stream())
         if rc != 0:
             raise RuntimeError(f"lnerf_adam_update: {last_error()}")
+
+
+_AUTOGRAD_FN = None
+
+
+def _autograd_fn():
+    """The torch.autograd.Function behind render_maps_autograd (built on first use: torch is optional
+    for the ctypes surface)."""
+    global _AUTOGRAD_FN
+    if _AUTOGRAD_FN is not None:
+        return _AUTOGRAD_FN
+    import torch
+
+    class RenderMapsFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, engine, mlp, cfg, ws, bs, x, dists, sample_t):
+            want = cfg["want"]
+            maps = engine.render_maps(mlp, ws, bs, x, dists, None, samples=cfg["samples"],
+                                      input_mode=cfg["input_mode"], num_freqs=cfg["num_freqs"],
+                                      near=cfg["near"], far=cfg["far"], sample_t=sample_t, flags=cfg["flags"],
+                                      want=tuple(want) + (("weights",) if cfg["t_grad"] and "weights" not in want
+                                                          else ()))
+            ctx.engine, ctx.mlp, ctx.cfg = engine, mlp, cfg
+            ctx.set_materialize_grads(False)   # a map the loss never used arrives as None: a NULL adjoint
+            ctx.save_for_backward(ws, bs, x, dists, sample_t, maps.weights if cfg["t_grad"] else None)
+            outs = tuple(getattr(maps, name) for name in want)
+            ctx.mark_non_differentiable(*[o for o, name in zip(outs, want) if name not in ADJOINT_NAMES])
+            return outs
+
+        @staticmethod
+        def backward(ctx, *gouts):
+            ws, bs, x, dists, sample_t, weights = ctx.saved_tensors
+            cfg, want = ctx.cfg, ctx.cfg["want"]
+            adj = {name: g.contiguous().float() for name, g in zip(want, gouts)
+                   if g is not None and name in ADJOINT_NAMES}
+            need_x = ctx.needs_input_grad[5]
+            need_dists = dists is not None and ctx.needs_input_grad[6]
+            r = ctx.engine.render_maps_vjp(ctx.mlp, ws, bs, x, dists, adj, samples=cfg["samples"],
+                                           input_mode=cfg["input_mode"], num_freqs=cfg["num_freqs"],
+                                           near=cfg["near"], far=cfg["far"], sample_t=sample_t,
+                                           flags=cfg["flags"], want_dists=need_dists, want_dinput=need_x)
+            d_t = None
+            if sample_t is not None and ctx.needs_input_grad[7] and "depth" in adj:
+                d_t = weights * adj["depth"][:, None]
+            return (None, None, None, r.d_ws.view_as(ws) if ctx.needs_input_grad[3] else None,
+                    r.d_bs.view_as(bs) if ctx.needs_input_grad[4] else None,
+                    r.d_input.view_as(x) if need_x else None, r.d_dists.view_as(dists) if need_dists else None, d_t)
+
+    _AUTOGRAD_FN = RenderMapsFn
+    return RenderMapsFn
+
+
+def render_maps_autograd(engine: Engine, mlp: LnerfMLP, ws, bs, x, dists, *, samples: int,
+                         input_mode: int = INPUT_POINTS, num_freqs: int = 5, sample_t=None,
+                         near: float = 2.0, far: float = 6.0, flags: int = 0,
+                         want=("color", "depth", "opacity", "weights")):
+    """The render maps as differentiable torch tensors: a torch.autograd.Function whose forward is
+    Engine.render_maps and whose backward is ONE Engine.render_maps_vjp call fed the gradients autograd
+    hands back for the maps. Returns the maps `want` names (ADJOINT_NAMES), in that order. Gradients
+    reach ws, bs, dists, x (through WANT_DINPUT, only if x requires grad) and sample_t
+    (weights * d_depth[:, None]); a map that is not asked for, or receives no gradient, contributes
+    nothing. Any torch loss on the maps can be trained this way, e.g.
+
+        color, depth, opacity = render_maps_autograd(eng, mlp, ws, bs, rays, None, samples=64,
+                                                     input_mode=INPUT_RAYS, want=("color", "depth", "opacity"))
+        loss = ((color + (1 - opacity)[:, None] * 1.0 - target) ** 2).sum() + 0.1 * (depth - d_gt).abs().sum()
+        loss.backward()      # ws.grad, bs.grad
+    """
+    unknown = set(want) - set(ADJOINT_NAMES)
+    if unknown or not want:
+        raise ValueError(f"want must name maps of {ADJOINT_NAMES}, got {tuple(want)}")
+    t_grad = sample_t is not None and bool(getattr(sample_t, "requires_grad", False)) and "depth" in want
+    cfg = dict(samples=samples, input_mode=input_mode, num_freqs=num_freqs, near=near, far=far, flags=flags,
+               want=tuple(want), t_grad=t_grad)
+    outs = _autograd_fn().apply(engine, mlp, cfg, ws, bs, x, dists, sample_t)
+    return outs
