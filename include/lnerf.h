@@ -337,6 +337,80 @@ int lnerf_ray_points(const float* rays, int n, int S, const float* sample_t, flo
 int lnerf_ray_points_grad(int n, int S, const float* sample_t, const float* d_points,
                           const float* scale, float* d_rays, void* stream);
 
+/* ---- Multiresolution hash grid ----------------------------------------------------------------
+ * A trainable scene representation between the sample points and the MLP: `levels` grids of
+ * increasing resolution over a box, F features per grid point, each level either stored densely or
+ * hashed into T = 2^log2_table entries; a point's encoding is the trilinear interpolation of its
+ * cell's eight corners at every level, (R, levels * F), ready for LNERF_INPUT_ENCODED with
+ * k[0] = levels * F. LNERF_WANT_DX returns d_encoded, lnerf_hashgrid_grad turns it into the
+ * gradients of the table and of the points, and lnerf_ray_points_grad / lnerf_pose_grad carry the
+ * latter to the camera. Free functions on a stream (no context, no workspace). An error returns a
+ * negative code, sets lnerf_last_error and launches and writes nothing; R == 0 succeeds and launches
+ * nothing (it does not zero d_table either). All pointers but the grid are device pointers. An
+ * extension: the reference's only encoder is pos_encoding.py.
+ *
+ * The table is (offset[levels], F) float32 row-major: level l owns entries offset[l] ..
+ * offset[l+1] - 1, of which it uses the first E_l = res[l]^3 if res[l]^3 <= T (a dense level),
+ * else T (a hashed one). The struct may be filled by lnerf_hashgrid_init or by hand; the entry
+ * points validate it on every call: 1 <= levels <= 32, F in {1, 2, 4, 8}, 4 <= log2_table <= 24,
+ * res[l] >= 2, offset[0] >= 0, offset[l+1] - offset[l] >= E_l, hi > lo (finite) on every axis.
+ * `table` must be aligned to min(16, 4 F) bytes (a row is one load up to 16 bytes).
+ *
+ * Per level l and coordinate c, in float64:
+ *   u_c = clamp(((double)p_c - lo_c) / ((double)hi_c - lo_c), 0, 1), a NaN taken as 0;
+ *   pos_c = u_c (res - 1);  i_c = min((int)floor(pos_c), res - 2);  w_c = pos_c - i_c.
+ * Corner k = 0..7 has bit c of k as its offset along c: grid point g_c = i_c + bit, factor w_c if
+ * the bit is set, else 1 - w_c; the corner's weight is (fx fy) fz. Its entry is
+ *   dense:  g_x + res (g_y + res g_z)
+ *   hashed: (g_x ^ g_y 2654435761u ^ g_z 805459861u) & (T - 1)   in uint32
+ * so every index is below E_l whatever the point holds (clamp first, hash after). */
+#define LNERF_HASHGRID_MAX_LEVELS 32
+typedef struct {
+    int levels;                                      /* 1..32 */
+    int features;                                    /* F in {1, 2, 4, 8} */
+    int log2_table;                                  /* T = 2^log2_table, 4..24 */
+    int res[LNERF_HASHGRID_MAX_LEVELS];              /* grid points per axis, >= 2 */
+    long long offset[LNERF_HASHGRID_MAX_LEVELS + 1]; /* level l's first entry; [levels] = total */
+    float lo[3], hi[3];                              /* the box; hi > lo */
+} lnerf_hashgrid;
+
+/* Host only (needs no device): fills *grid and returns the total number of entries, offset[levels],
+ * or a negative code (*grid is then untouched). res[l] = floor(base_res b^l + 0.5) in double with
+ * b = exp(ln(max_res / base_res) / (levels - 1)) (levels == 1: res[0] = base_res); 2 <= base_res <=
+ * max_res. offset[0] = 0 and each level's E_l is rounded up to a multiple of 4, so that every
+ * level's rows stay 16-byte aligned at F = 1. lo, hi: 3 host floats each. */
+long long lnerf_hashgrid_init(lnerf_hashgrid* grid, int levels, int features, int log2_table,
+                              int base_res, int max_res, const float* lo, const float* hi);
+
+/* encoded[r][l F + f] = (float) sum_{k=0..7} weight_k (double)table[offset_l + entry_k][f] for
+ * points (R, 3): float64 products (no FMA contraction) summed in the order of k from 0, rounded to
+ * float32 once; repeated calls give the same bits. A point outside the box encodes as the nearest
+ * point of the box, a NaN coordinate as lo_c. R <= 2^39. */
+int lnerf_hashgrid_encode(const lnerf_hashgrid* grid, const float* table, const float* points,
+                          long long R, float* encoded, void* stream);
+
+/* The reverse of lnerf_hashgrid_encode from d_encoded (R, levels * F). `scale` (nullable) is a
+ * device scalar multiplied in; `flags` is 0 or LNERF_ACCUMULATE. Either output may be NULL, both
+ * NULL is an error; `table` may be NULL when d_points is.
+ *   d_table (offset[levels], F): d_table[offset_l + entry_k][f] += (float)(scale weight_k
+ * d_encoded[r][l F + f]) over every row, level and corner; cells that collide in a hashed level sum.
+ * Without LNERF_ACCUMULATE the call first zeroes all offset[levels] * F values on the stream (entries
+ * no sample touches are +0); with it the call adds into what is there and untouched entries keep
+ * their bits. d_table is summed with float32 atomic adds (within a wave, adjacent rows that share an
+ * entry are added together first; small dense levels are summed per workgroup in LDS): its last bits
+ * depend on arrival order, so it is the ONE output of this library that is not bit-reproducible from
+ * call to call, unlike d_points and encoded. An entry that receives n terms is within
+ *     2^-23 |exact| + (n + 2) 2^-24 sum |term|
+ * of the exact sum (one float32 rounding per term and at most n float32 adds, in any order).
+ *   d_points (R, 3): d_points[r][c] = (float)(scale sum_l ((sum_f d_encoded[r][l F + f]
+ * (sum_k (d weight_k / d pos_c) table_k[f])) (res_l - 1) / (hi_c - lo_c))), d weight_k / d pos_x =
+ * +- fy fz (+ where bit x of k is set), likewise y and z; float64 in that fixed order, rounded once:
+ * repeated calls give the same bits. It is exactly 0 for a coordinate the clamp moved (outside the
+ * box; a coordinate on lo_c or hi_c itself counts as inside) and for a NaN. */
+int lnerf_hashgrid_grad(const lnerf_hashgrid* grid, const float* table, const float* points,
+                        long long R, const float* d_encoded, const float* scale, int flags,
+                        float* d_table, float* d_points, void* stream);
+
 /* Forward only (eval render, train_nerf.py:616-661, which always has a target image): acc_color
  * and the loss against batch->target. batch->target is required (NULL: an error, nothing is
  * launched or written); the loss is always computed and written to out->loss unless that is NULL.

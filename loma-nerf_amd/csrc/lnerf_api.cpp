@@ -23,6 +23,7 @@
 #include <sys/syscall.h>
 #include <unistd.h>
 
+#include "lnerf_hashgrid.h"
 #include "lnerf_internal.h"
 
 using namespace lnerf;
@@ -894,6 +895,141 @@ extern "C" int lnerf_ray_points_grad(int n, int S, const float* sample_t, const 
         need_device();
         k_ray_points_grad(n, S, sample_t, d_points, scale, d_rays, (hipStream_t)stream);
         check_launch("lnerf_ray_points_grad");
+    });
+}
+
+// ---- multiresolution hash grid (lnerf_hashgrid.hip): free functions on a stream, no context -------
+// A level's entry count before the rounding lnerf_hashgrid_init applies: res^3 if that fits the
+// table (dense), else T (hashed). T <= 2^24, so a dense level has res <= 256.
+static long long hashgrid_level_entries(int res, int log2_table, bool* dense) {
+    const long long T = 1ll << log2_table;
+    const bool d = res <= 256 && (long long)res * res * res <= T;
+    if (dense) *dense = d;
+    return d ? (long long)res * res * res : T;
+}
+
+static void hashgrid_check_shape(const char* what, int levels, int features, int log2_table) {
+    if (levels < 1 || levels > LNERF_HASHGRID_MAX_LEVELS)
+        fail("%s: levels = %d outside 1..%d", what, levels, LNERF_HASHGRID_MAX_LEVELS);
+    if (features != 1 && features != 2 && features != 4 && features != 8)
+        fail("%s: features = %d, need 1, 2, 4 or 8", what, features);
+    if (log2_table < 4 || log2_table > 24) fail("%s: log2_table = %d outside 4..24", what, log2_table);
+}
+
+// The validated, kernel-side form of `grid`; every index the kernels form is inside the level it
+// belongs to once this has passed.
+static HgParams hashgrid_params(const char* what, const lnerf_hashgrid* grid) {
+    if (!grid) fail("%s: grid is NULL", what);
+    hashgrid_check_shape(what, grid->levels, grid->features, grid->log2_table);
+    HgParams g{};
+    g.levels = grid->levels;
+    g.features = grid->features;
+    g.mask = (1u << grid->log2_table) - 1u;
+    if (grid->offset[0] < 0) fail("%s: offset[0] = %lld is negative", what, grid->offset[0]);
+    for (int l = 0; l < grid->levels; ++l) {
+        if (grid->res[l] < 2) fail("%s: res[%d] = %d, need at least 2", what, l, grid->res[l]);
+        bool dense = false;
+        const long long entries = hashgrid_level_entries(grid->res[l], grid->log2_table, &dense);
+        // (written as a comparison of offsets, so a huge offset cannot overflow the difference)
+        if (grid->offset[l + 1] < grid->offset[l] || grid->offset[l + 1] - grid->offset[l] < entries)
+            fail("%s: level %d (res %d) needs %lld entries, offset gives it %lld", what, l, grid->res[l], entries,
+                 grid->offset[l + 1] - grid->offset[l]);
+        g.lv[l].offset = grid->offset[l];
+        g.lv[l].res = grid->res[l];
+        g.lv[l].dense = dense ? 1 : 0;
+    }
+    if (grid->offset[grid->levels] > (1ll << 40)) fail("%s: more than 2^40 entries", what);
+    for (int c = 0; c < 3; ++c) {
+        if (!(grid->hi[c] > grid->lo[c]) || !std::isfinite(grid->hi[c]) || !std::isfinite(grid->lo[c]))
+            fail("%s: the box needs finite hi > lo on axis %d", what, c);
+        g.lo[c] = (double)grid->lo[c];
+        g.ext[c] = (double)grid->hi[c] - (double)grid->lo[c];
+    }
+    return g;
+}
+
+static void hashgrid_check_rows(const char* what, long long R) {
+    if (R < 0) fail("%s: negative row count %lld", what, R);
+    if (R > (long long)std::numeric_limits<int>::max() * 256) fail("%s: more than 2^39 rows", what);
+}
+
+// table rows are read as one 4 F-byte access up to 16 bytes
+static void hashgrid_check_aligned(const char* what, const char* name, const void* p, int features) {
+    const size_t a = features >= 4 ? 16 : 4 * (size_t)features;
+    if ((size_t)p % a) fail("%s: %s must be %zu-byte aligned at F = %d", what, name, a, features);
+}
+
+extern "C" long long lnerf_hashgrid_init(lnerf_hashgrid* grid, int levels, int features, int log2_table,
+                                         int base_res, int max_res, const float* lo, const float* hi) {
+    long long total = 0;
+    const int rc = guard_int([&]() {
+        const char* what = "lnerf_hashgrid_init";
+        if (!grid || !lo || !hi) fail("%s: null argument", what);
+        hashgrid_check_shape(what, levels, features, log2_table);
+        if (base_res < 2 || max_res < base_res) fail("%s: need 2 <= base_res <= max_res", what);
+        for (int c = 0; c < 3; ++c)
+            if (!(hi[c] > lo[c]) || !std::isfinite(hi[c]) || !std::isfinite(lo[c]))
+                fail("%s: the box needs finite hi > lo on axis %d", what, c);
+        lnerf_hashgrid g{};
+        g.levels = levels;
+        g.features = features;
+        g.log2_table = log2_table;
+        const double b = levels > 1 ? std::exp(std::log((double)max_res / (double)base_res) / (double)(levels - 1)) : 1.0;
+        for (int l = 0; l < levels; ++l) {
+            g.res[l] = (int)std::floor((double)base_res * std::pow(b, (double)l) + 0.5);
+            const long long entries = hashgrid_level_entries(g.res[l], log2_table, nullptr);
+            g.offset[l + 1] = g.offset[l] + (entries + 3) / 4 * 4;
+        }
+        for (int c = 0; c < 3; ++c) {
+            g.lo[c] = lo[c];
+            g.hi[c] = hi[c];
+        }
+        *grid = g;
+        total = g.offset[levels];
+    });
+    return rc ? rc : total;
+}
+
+extern "C" int lnerf_hashgrid_encode(const lnerf_hashgrid* grid, const float* table, const float* points,
+                                     long long R, float* encoded, void* stream) {
+    return guard_int([&]() {
+        const char* what = "lnerf_hashgrid_encode";
+        const HgParams g = hashgrid_params(what, grid);
+        if (!table || !points || !encoded) fail("%s: null argument", what);
+        hashgrid_check_aligned(what, "table", table, g.features);
+        hashgrid_check_rows(what, R);
+        if (R == 0) return;
+        need_device();
+        k_hashgrid_encode(g, table, points, R, encoded, (hipStream_t)stream);
+        check_launch(what);
+    });
+}
+
+extern "C" int lnerf_hashgrid_grad(const lnerf_hashgrid* grid, const float* table, const float* points,
+                                   long long R, const float* d_encoded, const float* scale, int flags,
+                                   float* d_table, float* d_points, void* stream) {
+    return guard_int([&]() {
+        const char* what = "lnerf_hashgrid_grad";
+        const HgParams g = hashgrid_params(what, grid);
+        if (flags & ~LNERF_ACCUMULATE) fail("%s: flags 0x%x: only LNERF_ACCUMULATE applies", what, flags);
+        if (!d_table && !d_points) fail("%s: d_table and d_points are both NULL", what);
+        if (!points || !d_encoded) fail("%s: null argument", what);
+        if (d_points && !table) fail("%s: d_points needs the table", what);
+        if (d_points) hashgrid_check_aligned(what, "table", table, g.features);
+        hashgrid_check_rows(what, R);
+        if (R == 0) return;
+        need_device();
+        hipStream_t s = (hipStream_t)stream;
+        if (d_table) {
+            if (!(flags & LNERF_ACCUMULATE))
+                HIP_OK(hipMemsetAsync(d_table, 0, (size_t)grid->offset[g.levels] * g.features * sizeof(float), s));
+            k_hashgrid_grad_table(g, points, R, d_encoded, scale, d_table, s);
+            check_launch(what);
+        }
+        if (d_points) {
+            k_hashgrid_grad_points(g, table, points, R, d_encoded, scale, d_points, s);
+            check_launch(what);
+        }
     });
 }
 

@@ -50,7 +50,8 @@ EXPORTED_SYMBOLS = [
     "lnerf_ctx_set_option", "lnerf_ctx_relu_masks", "lnerf_build_knobs", "lnerf_ctx_exceptional_rows",
     "lnerf_ctx_guard_fired", "lnerf_input_grad", "lnerf_pose_grad", "lnerf_ctx_workspace_used",
     "lnerf_render_maps", "lnerf_sample_stratified", "lnerf_sample_importance", "lnerf_ray_points",
-    "lnerf_ray_points_grad", "lnerf_render_maps_vjp",
+    "lnerf_ray_points_grad", "lnerf_render_maps_vjp", "lnerf_hashgrid_init", "lnerf_hashgrid_encode",
+    "lnerf_hashgrid_grad",
 ]
 
 # lnerf_ctx_last_path bits
@@ -91,6 +92,16 @@ class LnerfRenderOutputs(ctypes.Structure):
 class LnerfRenderAdjoints(ctypes.Structure):
     _fields_ = [("d_acc_color", ctypes.c_void_p), ("d_depth", ctypes.c_void_p), ("d_opacity", ctypes.c_void_p),
                 ("d_weights", ctypes.c_void_p), ("d_rgba", ctypes.c_void_p)]
+
+
+HASHGRID_MAX_LEVELS = 32
+
+
+class LnerfHashGrid(ctypes.Structure):
+    _fields_ = [("levels", ctypes.c_int), ("features", ctypes.c_int), ("log2_table", ctypes.c_int),
+                ("res", ctypes.c_int * HASHGRID_MAX_LEVELS),
+                ("offset", ctypes.c_longlong * (HASHGRID_MAX_LEVELS + 1)),
+                ("lo", ctypes.c_float * 3), ("hi", ctypes.c_float * 3)]
 
 
 _LIB = None
@@ -218,6 +229,14 @@ def configure(lib: ctypes.CDLL) -> None:
         for name in ("lnerf_sample_stratified", "lnerf_sample_importance", "lnerf_ray_points",
                      "lnerf_ray_points_grad"):
             getattr(lib, name).restype = ctypes.c_int
+    if hasattr(lib, "lnerf_hashgrid_encode"):   # (older in-tree A/B builds lack the hash grid)
+        vp, ci, ll, hg = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.POINTER(LnerfHashGrid)
+        lib.lnerf_hashgrid_init.argtypes = [hg, ci, ci, ci, ci, ci, _F, _F]
+        lib.lnerf_hashgrid_init.restype = ll
+        lib.lnerf_hashgrid_encode.argtypes = [hg, vp, vp, ll, vp, vp]
+        lib.lnerf_hashgrid_encode.restype = ci
+        lib.lnerf_hashgrid_grad.argtypes = [hg, vp, vp, ll, vp, vp, ci, vp, vp, vp]
+        lib.lnerf_hashgrid_grad.restype = ci
     for name in ("lnerf_ctx_timings", "lnerf_ctx_last_path", "lnerf_ctx_set_option", "lnerf_ctx_relu_masks",
                  "lnerf_ctx_exceptional_rows", "lnerf_ctx_guard_fired",
                  "lnerf_ctx_create", "lnerf_train_step", "lnerf_render",
@@ -246,6 +265,65 @@ def make_mlp(shapes, w_k: int, w_n: int) -> LnerfMLP:
 
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+class HashGrid:
+    """A multiresolution hash grid (lnerf.h "Multiresolution hash grid"): `levels` grids from base_res
+    to max_res points per axis over the box [lo, hi], `features` values per grid point, each level
+    dense or hashed into 2^log2_table entries. Wraps the lnerf_hashgrid struct that
+    lnerf_hashgrid_init fills (host only: no GPU is needed to build one). `struct` is what the entry
+    points take; its fields may also be set by hand (from_levels)."""
+
+    def __init__(self, levels: int = 16, features: int = 2, log2_table: int = 19, base_res: int = 16,
+                 max_res: int = 2048, lo=(-1.0, -1.0, -1.0), hi=(1.0, 1.0, 1.0)):
+        self.struct = LnerfHashGrid()
+        lo3, hi3 = (ctypes.c_float * 3)(*map(float, lo)), (ctypes.c_float * 3)(*map(float, hi))
+        total = load_library().lnerf_hashgrid_init(ctypes.byref(self.struct), int(levels), int(features),
+                                                   int(log2_table), int(base_res), int(max_res), lo3, hi3)
+        if total < 0:
+            raise ValueError(f"lnerf_hashgrid_init: {last_error()}")
+
+    @classmethod
+    def from_levels(cls, res, features: int, log2_table: int, lo, hi, align: int = 4):
+        """A grid with the given per-level resolutions, filled by hand: level l gets res^3 entries
+        if that is at most 2^log2_table, else 2^log2_table, rounded up to a multiple of `align`. The
+        library validates it when it is used."""
+        self = cls.__new__(cls)
+        g = self.struct = LnerfHashGrid()
+        g.levels, g.features, g.log2_table = len(res), int(features), int(log2_table)
+        off = 0
+        for l, r in enumerate(res):
+            g.res[l] = int(r)
+            g.offset[l] = off
+            off += -(-min(int(r) ** 3, 1 << int(log2_table)) // align) * align
+        g.offset[len(res)] = off
+        for c in range(3):
+            g.lo[c], g.hi[c] = float(lo[c]), float(hi[c])
+        return self
+
+    levels = property(lambda self: int(self.struct.levels))
+    features = property(lambda self: int(self.struct.features))
+    log2_table = property(lambda self: int(self.struct.log2_table))
+    res = property(lambda self: [int(self.struct.res[l]) for l in range(self.levels)])
+    offsets = property(lambda self: [int(self.struct.offset[l]) for l in range(self.levels + 1)])
+    lo = property(lambda self: [float(v) for v in self.struct.lo])
+    hi = property(lambda self: [float(v) for v in self.struct.hi])
+
+    @property
+    def total_entries(self) -> int:
+        return int(self.struct.offset[self.levels])
+
+    @property
+    def width(self) -> int:
+        """The encoding's width levels * F: the MLP's k[0]."""
+        return self.levels * self.features
+
+    def new_table(self, std: float = 1e-4, seed: int = 0, device="cuda:0"):
+        """A (total_entries, F) float32 table of normal(0, std) values from a seeded generator."""
+        import torch
+        gen = torch.Generator().manual_seed(int(seed))
+        t = torch.randn(self.total_entries, self.features, generator=gen, dtype=torch.float32) * float(std)
+        return t.to(device)
 
 
 @dataclass
@@ -630,6 +708,61 @@ class Engine:
             raise RuntimeError(f"lnerf_ray_points_grad: {last_error()}")
         return out
 
+    def hashgrid_encode(self, grid: HashGrid, table, points, out=None):
+        """lnerf_hashgrid_encode: the (R, grid.width) float32 encoding of points (R, 3) by `table`
+        (grid.total_entries, F): per level the trilinear interpolation of the cell's eight corners."""
+        self._f32("table", table, (grid.total_entries, grid.features))
+        if points.dim() != 2:
+            raise ValueError(f"points is {tuple(points.shape)}, expected (R, 3)")
+        R = points.shape[0]
+        self._f32("points", points, (R, 3))
+        if out is None:
+            out = self.torch.empty(R, grid.width, dtype=self.torch.float32, device=points.device)
+        else:
+            self._f32("out", out, (R, grid.width))
+        rc = self.lib.lnerf_hashgrid_encode(ctypes.byref(grid.struct), _ptr(table), _ptr(points), R, _ptr(out),
+                                            self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_hashgrid_encode: {last_error()}")
+        return out
+
+    def hashgrid_grad(self, grid: HashGrid, table, points, d_encoded, scale=None, accumulate: bool = False,
+                      d_table=None, want_d_points: bool = False, want_d_table: bool = True):
+        """lnerf_hashgrid_grad, the reverse of hashgrid_encode: (d_table (total_entries, F), d_points
+        (R, 3)) from d_encoded (R, grid.width) -- StepResult.d_x of an INPUT_ENCODED step with want_dx.
+        `d_table` may be a buffer to write (accumulate=True: to add into; it is then required); an
+        output that is not asked for is None. `table` may be None unless want_d_points. `scale` is an
+        optional float32 device scalar multiplied in. d_table is summed with float32 atomics (its last
+        bits vary from call to call); d_points is bit-reproducible."""
+        torch = self.torch
+        if points.dim() != 2:
+            raise ValueError(f"points is {tuple(points.shape)}, expected (R, 3)")
+        R = points.shape[0]
+        self._f32("points", points, (R, 3))
+        self._f32("d_encoded", d_encoded, (R, grid.width))
+        if table is not None:
+            self._f32("table", table, (grid.total_entries, grid.features))
+        if scale is not None:
+            self._f32("scale", scale)
+            if scale.numel() != 1:
+                raise ValueError("scale must hold one value")
+        if want_d_table:
+            if d_table is None:
+                if accumulate:
+                    raise ValueError("accumulate=True needs the d_table to add into")
+                d_table = torch.empty(grid.total_entries, grid.features, dtype=torch.float32, device=points.device)
+            else:
+                self._f32("d_table", d_table, (grid.total_entries, grid.features))
+        else:
+            d_table = None
+        d_points = torch.empty(R, 3, dtype=torch.float32, device=points.device) if want_d_points else None
+        rc = self.lib.lnerf_hashgrid_grad(ctypes.byref(grid.struct), _ptr(table), _ptr(points), R, _ptr(d_encoded),
+                                          _ptr(scale), ACCUMULATE if accumulate else 0, _ptr(d_table),
+                                          _ptr(d_points), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_hashgrid_grad: {last_error()}")
+        return d_table, d_points
+
     def timings(self):
         """Per-kernel ms of the last TIMING step: pack, fused, loss, dw, reduce, total."""
         out = (ctypes.c_float * 6)()
@@ -787,3 +920,48 @@ def render_maps_autograd(engine: Engine, mlp: LnerfMLP, ws, bs, x, dists, *, sam
                want=tuple(want), t_grad=t_grad)
     outs = _autograd_fn().apply(engine, mlp, cfg, ws, bs, x, dists, sample_t)
     return outs
+
+
+_HASHGRID_FN = None
+
+
+def _hashgrid_fn():
+    """The torch.autograd.Function behind hashgrid_autograd (built on first use, as _autograd_fn)."""
+    global _HASHGRID_FN
+    if _HASHGRID_FN is not None:
+        return _HASHGRID_FN
+    import torch
+
+    class HashGridFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, engine, grid, table, points):
+            ctx.engine, ctx.grid = engine, grid
+            ctx.save_for_backward(table, points)
+            return engine.hashgrid_encode(grid, table, points)
+
+        @staticmethod
+        def backward(ctx, g):
+            table, points = ctx.saved_tensors
+            need_t, need_p = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+            if not (need_t or need_p):
+                return None, None, None, None
+            d_table, d_points = ctx.engine.hashgrid_grad(ctx.grid, table, points, g.contiguous().float(),
+                                                         want_d_table=need_t, want_d_points=need_p)
+            return None, None, d_table, d_points
+
+    _HASHGRID_FN = HashGridFn
+    return HashGridFn
+
+
+def hashgrid_autograd(engine: Engine, grid: HashGrid, table, points):
+    """The hash-grid encoding as a differentiable torch tensor: a torch.autograd.Function whose forward
+    is Engine.hashgrid_encode and whose backward is ONE Engine.hashgrid_grad call. Gradients reach
+    `table` and, if it requires grad, `points`. Feed the result to a torch MLP, or to
+    render_maps_autograd(..., input_mode=INPUT_ENCODED) to train the grid under any loss on the maps:
+
+        x = hashgrid_autograd(eng, grid, table, points)
+        color, = render_maps_autograd(eng, mlp, ws, bs, x, dists, samples=S, input_mode=INPUT_ENCODED,
+                                      want=("color",))
+        ((color - target) ** 2).sum().backward()      # table.grad, ws.grad, bs.grad
+    """
+    return _hashgrid_fn().apply(engine, grid, table, points)
