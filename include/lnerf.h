@@ -411,6 +411,79 @@ int lnerf_hashgrid_grad(const lnerf_hashgrid* grid, const float* table, const fl
                         long long R, const float* d_encoded, const float* scale, int flags,
                         float* d_table, float* d_points, void* stream);
 
+/* ---- Occupancy grid ---------------------------------------------------------------------------
+ * Where the scene is empty, known without a network evaluation: a coarse grid of res^3 cells over
+ * a box that keeps a decayed running maximum of sigma per cell (`density`), its threshold packed
+ * into a bitfield (`bits`), and a sampler that marches each ray over the bitfield in M fixed steps
+ * and spreads the S samples over the occupied steps alone. The caller evaluates sigma at points
+ * inside cells (lnerf_occgrid_cell_points, then e.g. lnerf_render_maps' rgba), folds it in
+ * (lnerf_occgrid_update), thresholds (lnerf_occgrid_threshold) and samples (lnerf_sample_occupancy);
+ * lnerf_ray_points (points only) and LNERF_INPUT_POINTS / ENCODED with the sampler's dists and
+ * sample_t take it from there. Free functions on a stream (no context, no workspace). The struct is
+ * validated on every call. An error returns a negative code, sets lnerf_last_error and launches and
+ * writes nothing; n == 0 succeeds and launches nothing (lnerf_occgrid_update then skips the decay
+ * too). All pointers but the grid are device pointers. All arithmetic is float64 or integer, with one
+ * rounding to float32 at a store, and the only atomics are integer ones (a maximum, a count): every
+ * output has the same bits on every call. An extension: the reference samples linspace only
+ * (train_nerf.py:289-306).
+ *
+ * Cell (gx, gy, gz) has index c = gx + res (gy + res gz). `density` is res^3 float32, non-negative
+ * and finite (start from zeros); every call keeps that. `bits` is res^3 / 32 uint32: cell c is bit
+ * c & 31 of word c >> 5. */
+typedef struct {
+    int res;            /* cells per axis: a power of two, 4..256 (res^3 is a multiple of 64) */
+    float lo[3], hi[3]; /* the box; hi > lo, finite */
+} lnerf_occgrid;
+enum { LNERF_OCC_MEAN = 1, LNERF_OCC_LAST_OPAQUE = 2 };
+
+/* points (n, 3) inside the cells `cells` (n): p_c = (float)(lo_c + (g_c + u_c) / res (hi_c - lo_c))
+ * in float64 in that order, rounded once, with u (n, 3) clamped to [0, 1] and a NaN taken as 0 (the
+ * caller's random numbers); u == NULL means 0.5, the cell centre. cells == NULL means cell i is i
+ * and needs n == res^3. An index outside 0..res^3-1 gives the box centre (float)(lo_c + 0.5 (hi_c -
+ * lo_c)); lnerf_occgrid_update skips it. n <= 2^39. */
+int lnerf_occgrid_cell_points(const lnerf_occgrid* grid, const int* cells, long long n, const float* u,
+                              float* points, void* stream);
+
+/* The decayed running maximum. First every cell of `density` is multiplied by `decay` (float32, once
+ * per call; 0 <= decay <= 1, decay == 1 skips the pass). Then for i < n: density[cell_i] =
+ * max(density[cell_i], s_i) with s_i = sigma[i sigma_stride] (sigma_stride >= 1; 4 with sigma = rgba
+ * + 3 reads lnerf_render_maps' rgba in place). A NaN or a value <= 0 is ignored, +inf counts as
+ * FLT_MAX. cells as above (NULL: n == res^3); an index outside the grid is skipped; duplicate cells
+ * take the maximum (an integer atomic maximum on the float's bits: exact in any order). */
+int lnerf_occgrid_update(const lnerf_occgrid* grid, float* density, const int* cells, long long n,
+                         const float* sigma, int sigma_stride, float decay, void* stream);
+
+/* bits: bit c = (double)density[c] > thr with thr = threshold, or min(threshold, mean(density)) under
+ * LNERF_OCC_MEAN (the only flag). The mean is a float64 sum in two fixed-order stages divided by
+ * res^3, so it has the same bits on every call; a cell within res^3 2^-52 mean of the mean may fall
+ * on either side of what another summation order decides. *mean (that mean, whatever the flag) and
+ * *occupied (the number of set bits, exact) are nullable device scalars; bits is nullable too
+ * (statistics only); all three NULL is an error, and so is a NaN threshold. */
+int lnerf_occgrid_threshold(const lnerf_occgrid* grid, const float* density, float threshold, int flags,
+                            unsigned* bits, double* mean, long long* occupied, void* stream);
+
+/* Empty-space-skipping sample depths for rays (n, 6) = [o, d]: sample_t (n, S), dists (n, S) and
+ * n_occ (n), each nullable, not all three. steps = M, a multiple of 64 in 64..1024; 1 <= S <= 1024;
+ * far_t > near_t, both finite; u (n, S) clamped as above, NULL means 0.5; flags is 0 or
+ * LNERF_OCC_LAST_OPAQUE. n S <= 2^31 - 1. Per ray, in float64 with no FMA contraction:
+ *   h = ((double)far_t - (double)near_t) / M; step i has the midpoint c_i = near_t + (i + 0.5) h and
+ * the point p = (double)o + (double)d c_i; w_c = (p_c - lo_c) / ((double)hi_c - lo_c). Step i is
+ * occupied if 0 <= w_c < 1 on all three axes (a NaN fails) and the bit of the cell g_c =
+ * min((int)(w_c res), res - 1) is set. N = the number of occupied steps, written to n_occ. If
+ * N == 0 the ray is sampled as if every step were occupied (N' = M, else N' = N); n_occ still
+ * reports 0, so the caller can mask the ray.
+ *   Sample j: q = ((double)j + u_j) N' / S, k = min((long long)q, N' - 1), f = q - k, i = the index of
+ * the k-th occupied step counting from 0, t_j = (float)(near_t + (i + f) h). The depths are
+ * non-decreasing along a ray and each lies in an occupied step (to the one rounding).
+ *   dists_j = (float)(N' h / S) for every j -- each sample stands for an equal share of the occupied
+ * length; it is NOT the difference to the next sample, which would span the gaps -- and under
+ * LNERF_OCC_LAST_OPAQUE the last one is 1e8f, the reference's convention (train_nerf.py:306).
+ *   Every index depends on integer counts alone; the only floating-point values that reach a
+ * comparison are u and the cell test. */
+int lnerf_sample_occupancy(const lnerf_occgrid* grid, const unsigned* bits, const float* rays, int n,
+                           int S, int steps, float near_t, float far_t, const float* u, int flags,
+                           float* sample_t, float* dists, int* n_occ, void* stream);
+
 /* Forward only (eval render, train_nerf.py:616-661, which always has a target image): acc_color
  * and the loss against batch->target. batch->target is required (NULL: an error, nothing is
  * launched or written); the loss is always computed and written to out->loss unless that is NULL.

@@ -24,6 +24,7 @@
 #include <unistd.h>
 
 #include "lnerf_hashgrid.h"
+#include "lnerf_occgrid.h"
 #include "lnerf_internal.h"
 
 using namespace lnerf;
@@ -1030,6 +1031,108 @@ extern "C" int lnerf_hashgrid_grad(const lnerf_hashgrid* grid, const float* tabl
             k_hashgrid_grad_points(g, table, points, R, d_encoded, scale, d_points, s);
             check_launch(what);
         }
+    });
+}
+
+// ---- occupancy grid (lnerf_occgrid.hip): free functions on a stream, no context -------------------
+// The validated, kernel-side form of `grid`; every cell index the kernels form from a point or
+// accept from a list is inside 0..res^3-1 once this has passed.
+static OccParams occgrid_params(const char* what, const lnerf_occgrid* grid) {
+    if (!grid) fail("%s: grid is NULL", what);
+    const int res = grid->res;
+    if (res < 4 || res > 256 || (res & (res - 1))) fail("%s: res = %d, need a power of two in 4..256", what, res);
+    OccParams g{};
+    g.res = res;
+    while ((1 << g.shift) < res) ++g.shift;
+    g.cells = (long long)res * res * res;
+    for (int c = 0; c < 3; ++c) {
+        if (!(grid->hi[c] > grid->lo[c]) || !std::isfinite(grid->hi[c]) || !std::isfinite(grid->lo[c]))
+            fail("%s: the box needs finite hi > lo on axis %d", what, c);
+        g.lo[c] = (double)grid->lo[c];
+        g.ext[c] = (double)grid->hi[c] - (double)grid->lo[c];
+    }
+    return g;
+}
+
+// n cells of a list, or all res^3 of them in order when there is no list
+static void occgrid_check_cells(const char* what, const OccParams& g, const int* cells, long long n) {
+    if (n < 0) fail("%s: negative count %lld", what, n);
+    if (n > (long long)std::numeric_limits<int>::max() * 256) fail("%s: more than 2^39 cells", what);
+    if (!cells && n != 0 && n != g.cells)
+        fail("%s: n = %lld without a cell list, need res^3 = %lld", what, n, g.cells);
+}
+
+extern "C" int lnerf_occgrid_cell_points(const lnerf_occgrid* grid, const int* cells, long long n, const float* u,
+                                         float* points, void* stream) {
+    return guard_int([&]() {
+        const char* what = "lnerf_occgrid_cell_points";
+        const OccParams g = occgrid_params(what, grid);
+        if (!points) fail("%s: points is NULL", what);
+        occgrid_check_cells(what, g, cells, n);
+        if (n == 0) return;
+        need_device();
+        k_occgrid_cell_points(g, cells, n, u, points, (hipStream_t)stream);
+        check_launch(what);
+    });
+}
+
+extern "C" int lnerf_occgrid_update(const lnerf_occgrid* grid, float* density, const int* cells, long long n,
+                                    const float* sigma, int sigma_stride, float decay, void* stream) {
+    return guard_int([&]() {
+        const char* what = "lnerf_occgrid_update";
+        const OccParams g = occgrid_params(what, grid);
+        if (!density || !sigma) fail("%s: null argument", what);
+        if (sigma_stride < 1) fail("%s: sigma_stride = %d, need at least 1", what, sigma_stride);
+        if (!(decay >= 0.0f && decay <= 1.0f)) fail("%s: decay = %g outside 0..1", what, (double)decay);
+        occgrid_check_cells(what, g, cells, n);
+        if (n == 0) return;
+        need_device();
+        k_occgrid_update(g, density, cells, n, sigma, sigma_stride, decay, (hipStream_t)stream);
+        check_launch(what);
+    });
+}
+
+extern "C" int lnerf_occgrid_threshold(const lnerf_occgrid* grid, const float* density, float threshold, int flags,
+                                       unsigned* bits, double* mean, long long* occupied, void* stream) {
+    return guard_int([&]() {
+        const char* what = "lnerf_occgrid_threshold";
+        const OccParams g = occgrid_params(what, grid);
+        if (!density) fail("%s: density is NULL", what);
+        if (flags & ~LNERF_OCC_MEAN) fail("%s: flags 0x%x: only LNERF_OCC_MEAN applies", what, flags);
+        if (std::isnan(threshold)) fail("%s: threshold is NaN", what);
+        if (!bits && !mean && !occupied) fail("%s: bits, mean and occupied are all NULL", what);
+        need_device();
+        // the stage-1 partial sums and thr: stream-ordered scratch, so calls on several streams never share it
+        hipStream_t s = (hipStream_t)stream;
+        double* scratch = nullptr;
+        HIP_OK(hipMallocAsync((void**)&scratch, (size_t)occgrid_threshold_scratch(g) * sizeof(double), s));
+        k_occgrid_threshold(g, density, threshold, flags, bits, mean, occupied, scratch, s);
+        const hipError_t launched = hipGetLastError();
+        HIP_OK(hipFreeAsync(scratch, s));
+        if (launched != hipSuccess) fail("%s: kernel launch failed: %s", what, hipGetErrorString(launched));
+    });
+}
+
+extern "C" int lnerf_sample_occupancy(const lnerf_occgrid* grid, const unsigned* bits, const float* rays, int n,
+                                      int S, int steps, float near_t, float far_t, const float* u, int flags,
+                                      float* sample_t, float* dists, int* n_occ, void* stream) {
+    return guard_int([&]() {
+        const char* what = "lnerf_sample_occupancy";
+        const OccParams g = occgrid_params(what, grid);
+        if (!bits || !rays) fail("%s: null argument", what);
+        if (steps < 64 || steps > 1024 || steps % 64)
+            fail("%s: steps = %d, need a multiple of 64 in 64..1024", what, steps);
+        if (S < 1 || S > 1024) fail("%s: S = %d outside 1..1024", what, S);
+        if (!(far_t > near_t) || !std::isfinite(far_t) || !std::isfinite(near_t))
+            fail("%s: need finite far_t > near_t", what);
+        if (flags & ~LNERF_OCC_LAST_OPAQUE) fail("%s: flags 0x%x: only LNERF_OCC_LAST_OPAQUE applies", what, flags);
+        if (!sample_t && !dists && !n_occ) fail("%s: sample_t, dists and n_occ are all NULL", what);
+        check_rows(what, n, S);
+        if (n == 0) return;
+        need_device();
+        k_sample_occupancy(g, bits, rays, n, S, steps, near_t, far_t, u, flags, sample_t, dists, n_occ,
+                           (hipStream_t)stream);
+        check_launch(what);
     });
 }
 

@@ -51,7 +51,8 @@ EXPORTED_SYMBOLS = [
     "lnerf_ctx_guard_fired", "lnerf_input_grad", "lnerf_pose_grad", "lnerf_ctx_workspace_used",
     "lnerf_render_maps", "lnerf_sample_stratified", "lnerf_sample_importance", "lnerf_ray_points",
     "lnerf_ray_points_grad", "lnerf_render_maps_vjp", "lnerf_hashgrid_init", "lnerf_hashgrid_encode",
-    "lnerf_hashgrid_grad",
+    "lnerf_hashgrid_grad", "lnerf_occgrid_cell_points", "lnerf_occgrid_update", "lnerf_occgrid_threshold",
+    "lnerf_sample_occupancy",
 ]
 
 # lnerf_ctx_last_path bits
@@ -102,6 +103,14 @@ class LnerfHashGrid(ctypes.Structure):
                 ("res", ctypes.c_int * HASHGRID_MAX_LEVELS),
                 ("offset", ctypes.c_longlong * (HASHGRID_MAX_LEVELS + 1)),
                 ("lo", ctypes.c_float * 3), ("hi", ctypes.c_float * 3)]
+
+
+OCC_MEAN = 1          # lnerf_occgrid_threshold: thr = min(threshold, mean(density))
+OCC_LAST_OPAQUE = 2   # lnerf_sample_occupancy: the last dist of every ray is 1e8
+
+
+class LnerfOccGrid(ctypes.Structure):
+    _fields_ = [("res", ctypes.c_int), ("lo", ctypes.c_float * 3), ("hi", ctypes.c_float * 3)]
 
 
 _LIB = None
@@ -237,6 +246,16 @@ def configure(lib: ctypes.CDLL) -> None:
         lib.lnerf_hashgrid_encode.restype = ci
         lib.lnerf_hashgrid_grad.argtypes = [hg, vp, vp, ll, vp, vp, ci, vp, vp, vp]
         lib.lnerf_hashgrid_grad.restype = ci
+    if hasattr(lib, "lnerf_sample_occupancy"):   # (older in-tree A/B builds lack the occupancy grid)
+        vp, ci, cf, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
+        og = ctypes.POINTER(LnerfOccGrid)
+        lib.lnerf_occgrid_cell_points.argtypes = [og, vp, ll, vp, vp, vp]
+        lib.lnerf_occgrid_update.argtypes = [og, vp, vp, ll, vp, ci, cf, vp]
+        lib.lnerf_occgrid_threshold.argtypes = [og, vp, cf, ci, vp, vp, vp, vp]
+        lib.lnerf_sample_occupancy.argtypes = [og, vp, vp, ci, ci, ci, cf, cf, vp, ci, vp, vp, vp, vp]
+        for name in ("lnerf_occgrid_cell_points", "lnerf_occgrid_update", "lnerf_occgrid_threshold",
+                     "lnerf_sample_occupancy"):
+            getattr(lib, name).restype = ci
     for name in ("lnerf_ctx_timings", "lnerf_ctx_last_path", "lnerf_ctx_set_option", "lnerf_ctx_relu_masks",
                  "lnerf_ctx_exceptional_rows", "lnerf_ctx_guard_fired",
                  "lnerf_ctx_create", "lnerf_train_step", "lnerf_render",
@@ -324,6 +343,39 @@ class HashGrid:
         gen = torch.Generator().manual_seed(int(seed))
         t = torch.randn(self.total_entries, self.features, generator=gen, dtype=torch.float32) * float(std)
         return t.to(device)
+
+
+class OccGrid:
+    """An occupancy grid (lnerf.h "Occupancy grid"): res^3 cells over the box [lo, hi], res a power
+    of two in 4..256. It owns no device memory: `density` (num_cells float32, a decayed running
+    maximum of sigma) and `bits` (num_cells / 32 int32 words, cell c = bit c & 31 of word c >> 5) are
+    the caller's tensors, made by new_density / new_bits. `struct` is what the entry points take; the
+    library validates it on every call."""
+
+    def __init__(self, res: int = 128, lo=(-1.0, -1.0, -1.0), hi=(1.0, 1.0, 1.0)):
+        g = self.struct = LnerfOccGrid()
+        g.res = int(res)
+        for c in range(3):
+            g.lo[c], g.hi[c] = float(lo[c]), float(hi[c])
+
+    res = property(lambda self: int(self.struct.res))
+    lo = property(lambda self: [float(v) for v in self.struct.lo])
+    hi = property(lambda self: [float(v) for v in self.struct.hi])
+
+    @property
+    def num_cells(self) -> int:
+        return self.res ** 3
+
+    def new_density(self, device="cuda:0"):
+        """(num_cells,) float32 zeros."""
+        import torch
+        return torch.zeros(self.num_cells, dtype=torch.float32, device=device)
+
+    def new_bits(self, device="cuda:0"):
+        """(num_cells / 32,) int32 zeros: the bitfield's uint32 words (torch has no uint32 arithmetic;
+        the bit patterns are the library's)."""
+        import torch
+        return torch.zeros(self.num_cells // 32, dtype=torch.int32, device=device)
 
 
 @dataclass
@@ -762,6 +814,116 @@ class Engine:
         if rc != 0:
             raise RuntimeError(f"lnerf_hashgrid_grad: {last_error()}")
         return d_table, d_points
+
+    def _dev(self, name, t, dtype, shape=None):
+        """`t` must be a contiguous tensor of `dtype` on this engine's device (of `shape`, if given)."""
+        torch = self.torch
+        if not torch.is_tensor(t) or t.dtype != dtype:
+            raise ValueError(f"{name} must be a {str(dtype).replace('torch.', '')} tensor")
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"{name} must live on cuda:{self.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} is {tuple(t.shape)}, expected {tuple(shape)}")
+        return t
+
+    def _occ_cells(self, occ, cells):
+        """The length of the optional int32 cell list (None: every cell in order)."""
+        if cells is None:
+            return occ.num_cells
+        self._dev("cells", cells, self.torch.int32)
+        if cells.dim() != 1:
+            raise ValueError(f"cells is {tuple(cells.shape)}, expected (n,)")
+        return cells.shape[0]
+
+    def occgrid_cell_points(self, occ: OccGrid, cells=None, u=None):
+        """lnerf_occgrid_cell_points: (n, 3) float32 points inside the cells `cells` (n,) int32 (None:
+        all num_cells cells in order), placed by u (n, 3) in [0, 1] (None: the cell centres). An index
+        outside the grid gives the box centre."""
+        n = self._occ_cells(occ, cells)
+        if u is not None:
+            self._f32("u", u, (n, 3))
+        out = self.torch.empty(n, 3, dtype=self.torch.float32, device=f"cuda:{self.device}")
+        rc = self.lib.lnerf_occgrid_cell_points(ctypes.byref(occ.struct), _ptr(cells), n, _ptr(u), _ptr(out),
+                                                self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_occgrid_cell_points: {last_error()}")
+        return out
+
+    def occgrid_update(self, occ: OccGrid, density, sigma, cells=None, decay: float = 0.95, sigma_stride: int = 1):
+        """lnerf_occgrid_update, in place on density (num_cells,): density *= decay, then
+        density[cells[i]] = max(density[cells[i]], sigma.flatten()[i * sigma_stride]). `sigma` is any
+        contiguous float32 tensor holding at least (n - 1) * sigma_stride + 1 values, e.g. an (n,)
+        vector, or rgba.flatten()[3:] with sigma_stride=4. Returns density."""
+        self._f32("density", density, (occ.num_cells,))
+        n = self._occ_cells(occ, cells)
+        self._f32("sigma", sigma)
+        if sigma_stride < 1:
+            raise ValueError("sigma_stride must be at least 1")
+        if n and sigma.numel() < (n - 1) * int(sigma_stride) + 1:
+            raise ValueError(f"sigma holds {sigma.numel()} values, {n} cells at stride {sigma_stride} "
+                             f"need {(n - 1) * int(sigma_stride) + 1}")
+        rc = self.lib.lnerf_occgrid_update(ctypes.byref(occ.struct), _ptr(density), _ptr(cells), n, _ptr(sigma),
+                                           int(sigma_stride), float(decay), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_occgrid_update: {last_error()}")
+        return density
+
+    def occgrid_threshold(self, occ: OccGrid, density, threshold: float = 0.01, use_mean: bool = True, bits=None,
+                          want=("bits", "mean", "occupied")):
+        """lnerf_occgrid_threshold: (bits, mean, occupied). bits (num_cells / 32,) int32 words with bit
+        c = density[c] > thr, thr = threshold or, with use_mean, min(threshold, mean(density)); mean a
+        float64 and occupied an int64 device scalar (the mean of density, the number of set bits).
+        `bits` may be a buffer to write; an entry `want` does not name is None."""
+        torch = self.torch
+        unknown = set(want) - {"bits", "mean", "occupied"}
+        if unknown or not want:
+            raise ValueError(f"want must name 'bits', 'mean' and / or 'occupied', got {tuple(want)}")
+        self._f32("density", density, (occ.num_cells,))
+        if "bits" not in want:
+            bits = None
+        elif bits is None:
+            bits = torch.empty(occ.num_cells // 32, dtype=torch.int32, device=density.device)
+        else:
+            self._dev("bits", bits, torch.int32, (occ.num_cells // 32,))
+        mean = torch.empty((), dtype=torch.float64, device=density.device) if "mean" in want else None
+        occupied = torch.empty((), dtype=torch.int64, device=density.device) if "occupied" in want else None
+        rc = self.lib.lnerf_occgrid_threshold(ctypes.byref(occ.struct), _ptr(density), float(threshold),
+                                              OCC_MEAN if use_mean else 0, _ptr(bits), _ptr(mean), _ptr(occupied),
+                                              self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_occgrid_threshold: {last_error()}")
+        return bits, mean, occupied
+
+    def sample_occupancy(self, occ: OccGrid, bits, rays, samples: int, steps: int = 1024, near: float = 2.0,
+                         far: float = 6.0, u=None, last_opaque: bool = False, want=("t", "dists", "n_occ")):
+        """lnerf_sample_occupancy: (sample_t (n, samples), dists (n, samples), n_occ (n,) int32) for rays
+        (n, 6). Each ray is marched in `steps` steps over the bitfield and its samples are spread over
+        the occupied steps alone, placed by u (n, samples) in [0, 1] (None: 0.5). dists is the equal
+        share of the occupied length each sample stands for (last_opaque: the last one is 1e8); n_occ
+        the number of occupied steps -- 0 marks a ray that met nothing, sampled over [near, far] as a
+        whole. An entry `want` does not name is None."""
+        torch = self.torch
+        unknown = set(want) - {"t", "dists", "n_occ"}
+        if unknown or not want:
+            raise ValueError(f"want must name 't', 'dists' and / or 'n_occ', got {tuple(want)}")
+        self._dev("bits", bits, torch.int32, (occ.num_cells // 32,))
+        if rays.dim() != 2:
+            raise ValueError(f"rays is {tuple(rays.shape)}, expected (n, 6)")
+        n, S = rays.shape[0], int(samples)
+        self._f32("rays", rays, (n, 6))
+        if u is not None:
+            self._f32("u", u, (n, S))
+        t = torch.empty(n, max(S, 0), dtype=torch.float32, device=rays.device) if "t" in want else None
+        dists = torch.empty(n, max(S, 0), dtype=torch.float32, device=rays.device) if "dists" in want else None
+        n_occ = torch.empty(n, dtype=torch.int32, device=rays.device) if "n_occ" in want else None
+        rc = self.lib.lnerf_sample_occupancy(ctypes.byref(occ.struct), _ptr(bits), _ptr(rays), n, S, int(steps),
+                                             float(near), float(far), _ptr(u), OCC_LAST_OPAQUE if last_opaque else 0,
+                                             _ptr(t), _ptr(dists), _ptr(n_occ), self._stream())
+        if rc != 0:
+            raise RuntimeError(f"lnerf_sample_occupancy: {last_error()}")
+        return t, dists, n_occ
 
     def timings(self):
         """Per-kernel ms of the last TIMING step: pack, fused, loss, dw, reduce, total."""

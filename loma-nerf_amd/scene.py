@@ -175,6 +175,44 @@ def hashgrid_step(engine, grid, table, mlp, ws, bs, rays, sample_t, target, *, s
                 d_table=d_table, d_points=d_points, d_rays=d_rays)
 
 
+def occgrid_refresh(engine, occ, density, bits, sigma_fn, *, cells=None, u=None, decay=0.95, threshold=0.01,
+                    use_mean=True):
+    """One refresh of an occupancy grid (an extension; the reference has none): Engine.occgrid_cell_points
+    places a point in each cell of `cells` (n,) int32 (None: every cell) by u (n, 3) (None: the centres),
+    `sigma_fn(points) -> (n,)` float32 is the caller's density there -- e.g. the last column of
+    engine.render_maps(..., want=("rgba",)).rgba on POINTS or on hash-grid ENCODED rows with samples=1 --
+    Engine.occgrid_update folds it into `density` (decayed running maximum, in place) and
+    Engine.occgrid_threshold rewrites `bits` in place. Returns (mean, occupied) device scalars."""
+    points = engine.occgrid_cell_points(occ, cells, u)
+    sigma = sigma_fn(points)
+    if tuple(sigma.shape) != (points.shape[0],):
+        raise ValueError(f"sigma_fn returned {tuple(sigma.shape)}, expected ({points.shape[0]},)")
+    engine.occgrid_update(occ, density, sigma.contiguous(), cells=cells, decay=decay)
+    _, mean, occupied = engine.occgrid_threshold(occ, density, threshold, use_mean=use_mean, bits=bits)
+    return mean, occupied
+
+
+def render_occupancy_image(engine, mlp, ws, bs, occ, bits, width, K, c2w, samples, num_freqs, steps=1024, near=2.0,
+                           far=6.0, flags=0, rays=None, u=None, last_opaque=False,
+                           want=("color", "depth", "opacity")):
+    """A novel view with empty-space skipping (an extension; the reference samples one fixed grid):
+    get_rays for the full width x width frame, Engine.sample_occupancy spreads `samples` depths per ray
+    over the steps the bitfield marks occupied (u: optional (rays, samples) random numbers, None = the
+    midpoints), Engine.ray_points turns them into points, and the network renders those
+    (LNERF_INPUT_POINTS) with the sampler's dists and sample_t. Returns (lnerf.RenderMaps, n_occ);
+    n_occ (rays,) int32 is 0 for a ray that met no occupied step (sampled over [near, far] as a whole:
+    the caller may mask it)."""
+    import lnerf
+    if rays is None:
+        rays = engine.get_rays(width, K, c2w)
+    t, dists, n_occ = engine.sample_occupancy(occ, bits, rays, samples, steps=steps, near=near, far=far, u=u,
+                                              last_opaque=last_opaque)
+    points, _ = engine.ray_points(rays, t)
+    maps = engine.render_maps(mlp, ws, bs, points, dists, None, samples=samples, input_mode=lnerf.INPUT_POINTS,
+                              num_freqs=num_freqs, sample_t=t, flags=flags, want=want)
+    return maps, n_occ
+
+
 def step_flops(shapes):
     """Canonical algorithmic FLOPs per sample: fwd 2KN every layer, bwd dW 2KN
     every layer, bwd dX 2KN for l >= 1."""
