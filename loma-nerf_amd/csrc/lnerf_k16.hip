@@ -21,6 +21,7 @@
 // reads (lnerf_fused.hip slab_off): a wave owns one 16-sample half of a 32-sample block.
 #include "lnerf_composite.h"
 #include "lnerf_internal.h"
+#include "lnerf_wave_addr.h"
 
 #include <stddef.h>
 #include <stdio.h>
@@ -147,25 +148,6 @@ struct K16Args {
 #endif
 };
 
-__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
-
-// LDS byte address of a pointer into __shared__ memory.
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)p;
-}
-
-// One LDS-DMA wave instruction (global_load_lds_dwordx4: 16 B per lane, lane-linear into the
-// wave-uniform LDS address `lds`), from inline asm with M0 written in the same statement.
-// Why asm: an LDS-DMA the compiler can see makes it wait vmcnt(0) before every later LDS read
-// (it cannot tell the ring slots apart), which would drain the next chunk's DMA; hidden from it,
-// the transfer has no register destination (nothing the compiler could copy or reuse early) and
-// its completion is counted by hand (dma_barrier's vmcnt). The `s_nop 0` is the M0-write ->
-// LDS-DMA wait state. No compiler code in these kernels reads M0 (tests/test_isa.py checks it).
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc),
-                 "s"(__builtin_amdgcn_readfirstlane(lds)));
-}
-
 // ---- optional in-kernel phase timing (-DLNERF_PROF=1, never in the product build): per-wave
 // s_memtime deltas, lane 0 accumulating in LDS, summed into g_k16_prof at the end.
 #ifndef LNERF_PROF
@@ -212,25 +194,31 @@ __device__ __forceinline__ ChunkT chunk_at(const K16Args& a, int ci) {
     return ChunkT{bytes ? a.w16 + off : nullptr, bytes, (int)(e >> 16) - 1};
 }
 
-// LDS-DMA (global_load_lds_dwordx4) of a chunk into its ring slot: 8 KiB per round of the
-// workgroup, each wave instruction 1 KiB (lane-linear); the last wave also stages the biases a
-// first forward chunk carries (bias ring slot l % 3). Returns the instructions this wave issued
-// (what a later vmcnt must leave outstanding).
+// The biases a first forward chunk carries: one more piece (256 floats) from the last wave into
+// bias ring slot l % 3. Returns the instructions issued (0 or 1).
 template <int NW>
-__device__ __forceinline__ int dma_chunk(const K16Args& a, const ChunkT& c, unsigned char* dst,
-                                         float* bias_ring) {
-    const int tid = threadIdx.x, wave = wave_id();
-    int n = 0;
+__device__ __forceinline__ int dma_bias(const K16Args& a, const WaveCtx& wc, const ChunkT& c) {
+    if (c.bias < 0 || wc.wave != NW - 1) return 0;
+    glds16s(a.b16 + (size_t)c.bias * 256, wc.lane16, wc.bias_ring + (unsigned)(c.bias % 3) * 1024u);
+    return 1;
+}
+
+// LDS-DMA (global_load_lds_dwordx4) of a chunk into its ring slot (`slot`: the slot's LDS byte
+// address): 8 KiB per round of the workgroup, each wave instruction 1 KiB (lane-linear) from a
+// scalar base; the last wave also stages the biases a first forward chunk carries (bias ring slot
+// l % 3). Returns the instructions this wave issued (what a later vmcnt must leave outstanding).
+template <int NW>
+__device__ __forceinline__ int dma_chunk(const K16Args& a, const WaveCtx& wc, const ChunkT& c, unsigned slot) {
     if (!c.src) return 0;
-    for (int off = wave * 1024; off < c.bytes; off += NW * 1024) {
-        glds16((const char*)c.src + off + (tid & 63) * 16, lds_addr(dst + off));
-        ++n;
+    const int n = waddr::dma_piece_count(c.bytes, wc.wave, NW);
+    const char* src = (const char*)c.src + wc.woff;
+    unsigned dst = slot + wc.woff;
+    for (int p = 0; p < n; ++p) {
+        glds16s(src, wc.lane16, dst);
+        src += waddr::dma_piece_stride(NW);
+        dst += waddr::dma_piece_stride(NW);
     }
-    if (c.bias >= 0 && wave == NW - 1) {
-        glds16(a.b16 + (size_t)c.bias * 256 + (tid & 63) * 4, lds_addr(bias_ring + (c.bias % 3) * 256));
-        ++n;
-    }
-    return n;
+    return n + dma_bias<NW>(a, wc, c);
 }
 
 // The chunk the next k-step reads has landed (this wave's pieces: vector-memory operations retire
@@ -304,14 +292,44 @@ __device__ __forceinline__ void split_x(float x, __bf16& h, __bf16& m, __bf16& l
     l = (__bf16)(r - (float)m);
 }
 
+// A wave-uniform store base, materialised in a scalar register pair here (an empty asm that takes and
+// returns it in place, no instruction): the address of the store is then scalar pair + the lane's
+// 32-bit offset + immediate, which the compiler selects as the SGPR-base form of global_store. Left
+// transparent, it folds the lane offset into the slab pointer once per pass (a 64-bit vector pair)
+// and adds every k-step's offset to that per lane (v_lshl_add_u64, v_add_co / v_addc_co per store).
+// (The address is rebuilt from the integer, as a global-memory pointer: behind the asm the compiler
+// no longer knows the address space and would emit flat stores.)
+__device__ __forceinline__ unsigned long long scalar_base(const void* p) {
+    unsigned long long b = (unsigned long long)p;
+    asm("" : "+s"(b));
+    return b;
+}
+// The lane's 32-bit offset, taken and returned in place next to the stores that use it: its
+// zero-extension then sits in the stores' own basic block, where instruction selection can see
+// "scalar pair + zext(32-bit vector)" (hoisted out of the pass, the extension becomes a 64-bit
+// vector pair and every store a 64-bit vector add again).
+__device__ __forceinline__ unsigned lane_off_here(unsigned v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
+template <typename V>
+__device__ __forceinline__ void store_nt_at(const V& v, unsigned long long sbase, unsigned voff, unsigned imm) {
+    typedef __attribute__((address_space(1))) V GV;
+    __builtin_nontemporal_store(v, (GV*)((sbase + (unsigned long long)voff) + imm));
+}
+
 // Slab tile store: the 8 features of k-step s that a lane holds for its sample n (registers 0-3 of
 // tiles 2s and 2s+1 = features 4g ..+3 and 16 + 4g ..+3 of the 32-feature tile) into this wave's
 // sample-major half-block [feature half 2][16 samples][16 features]: two global_store_dwordx4,
 // each wave instruction one contiguous 1 KiB (lnerf_dw16.hip reads it back transposed).
-__device__ __forceinline__ void store_slab_step(float* __restrict__ dst, const fx4& t0, const fx4& t1) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
-    __builtin_nontemporal_store(t0, (fx4*)(dst + n * 16 + 4 * g));
-    __builtin_nontemporal_store(t1, (fx4*)(dst + 256 + n * 16 + 4 * g));
+// The address is the wave-uniform `dst` (a scalar pair) plus the lane's constant byte offset
+// wc.lane_f32 (the SGPR-base form of the store: no per-lane 64-bit address is built).
+__device__ __forceinline__ void store_slab_step(const WaveCtx& wc, float* __restrict__ dst, const fx4& t0,
+                                                const fx4& t1) {
+    const unsigned long long b = scalar_base(dst);
+    const unsigned vo = lane_off_here(wc.lane_f32);
+    store_nt_at(t0, b, vo, 0);
+    store_nt_at(t1, b, vo, waddr::kSlabHalfF32);
 }
 
 // The same k-step store for an int24 activation slab (lnerf_internal.h a24_slabs): the 8 values
@@ -337,14 +355,17 @@ __device__ __forceinline__ Packed24 pack_slab_step24(const fx4& t0, const fx4& t
 // two global_store_dwordx3 into the 1.5-KiB half-block run [feature half 2][16 samples][16 f] x 3 B
 // (4-byte aligned: the 12-B runs sit at 12 g; a plain 3-vector claims 16-B size and alignment,
 // which would let the compiler widen the store over the neighbouring lane's bytes)
-__device__ __forceinline__ void store_packed24(unsigned char* __restrict__ dst, const Packed24& v) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, n = lane & 15;
-    __builtin_nontemporal_store(v.p0, (u3a*)(dst + n * 48 + 12 * g));
-    __builtin_nontemporal_store(v.p1, (u3a*)(dst + 768 + n * 48 + 12 * g));
+// (wave-uniform `dst` plus the lane's constant byte offset wc.lane_24, as store_slab_step)
+__device__ __forceinline__ void store_packed24(const WaveCtx& wc, unsigned char* __restrict__ dst,
+                                               const Packed24& v) {
+    const unsigned long long b = scalar_base(dst);
+    const unsigned vo = lane_off_here(wc.lane_24);
+    store_nt_at(v.p0, b, vo, 0);
+    store_nt_at(v.p1, b, vo, waddr::kSlabHalf24);
 }
-__device__ __forceinline__ void store_slab_step24(unsigned char* __restrict__ dst, const fx4& t0, const fx4& t1,
-                                                  int ex) {
-    store_packed24(dst, pack_slab_step24(t0, t1, ex));
+__device__ __forceinline__ void store_slab_step24(const WaveCtx& wc, unsigned char* __restrict__ dst, const fx4& t0,
+                                                  const fx4& t1, int ex) {
+    store_packed24(wc, dst, pack_slab_step24(t0, t1, ex));
 }
 
 // Materialise a value here: an empty asm that reads and writes it in place (no instruction; the
@@ -432,21 +453,22 @@ constexpr int pass_kc() {
 #endif
 constexpr int kPiecesMax = 8;   // pieces per wave of a full chunk (64 KiB / 8 waves, 32 KiB / 4; NG = 2: 16)
 struct DmaJob {
-    const char* src = nullptr;   // the wave's (uniform) address of piece 0
-    unsigned char* dst = nullptr;   // LDS address of this wave's piece 0
+    const char* src = nullptr;   // the wave's (uniform) address of piece 0: a scalar pair
+    unsigned dst = 0;            // LDS byte address of this wave's piece 0 (scalar)
     int n = 0;                   // this wave's pieces of the chunk
+    unsigned lane16 = 0;         // WaveCtx::lane16, the only vector operand of a piece
 };
-template <int NW>
-__device__ __forceinline__ void dma_piece(const DmaJob& j, int p) {
-    const int lane = threadIdx.x & 63;
-    glds16(j.src + p * (NW * 1024) + lane * 16, lds_addr(j.dst + p * (NW * 1024)));
+// piece P: the source base advances in scalar registers, M0 takes dst + P NW KiB in one scalar add
+template <int NW, int P>
+__device__ __forceinline__ void dma_piece(const DmaJob& j) {
+    glds16s_at<waddr::dma_piece_off(P, NW)>(j.src + waddr::dma_piece_off(P, NW), j.lane16, j.dst);
 }
 // the pieces that land on output tile O: p with p * NTO / kPiecesMax == O (all on tile 0 when NTO == 1);
 // FULL: the chunk is known to be whole (every wave issues kPiecesMax pieces, no per-piece test)
 template <int NTO, int O, int NW, bool FULL, int... P>
 __device__ __forceinline__ void dma_pieces_at(const DmaJob& j, std::integer_sequence<int, P...>) {
     constexpr int KP = sizeof...(P);
-    (((P * NTO) / KP == O ? ((FULL || P < j.n) ? dma_piece<NW>(j, P) : void()) : void()), ...);
+    (((P * NTO) / KP == O ? ((FULL || P < j.n) ? dma_piece<NW, P>(j) : void()) : void()), ...);
 }
 
 // Output tile O of one k-step: issue the reads of tile O + kDist, the MFMAs of tile O (small
@@ -610,7 +632,7 @@ __device__ __forceinline__ void make_b(const fx4 (&in)[kMaxT], int s, int ex, bf
 // pass): kPiecesMax pieces per wave with no per-piece test and no byte arithmetic.
 template <int NTO, int PL, int NW, int NG, int FDP = 0, bool A24 = false>
 __device__ __forceinline__ void k16_step(const K16Args& a, int ks, int s, int kk, bool last, int& ci,
-                                         unsigned char* ring, float* bias_ring, const fx4 (&in)[NG][kMaxT],
+                                         unsigned char* ring, const WaveCtx& wc, const fx4 (&in)[NG][kMaxT],
                                          fx4 (&out)[NG][kMaxT], float* const (&slab)[NG], const int (&ex)[NG],
                                          bf8 (&bh)[NG], bf8 (&bm)[NG], bf8 (&bl)[NG], int& pending,
                                          const unsigned short* fdsrc) {
@@ -631,29 +653,24 @@ __device__ __forceinline__ void k16_step(const K16Args& a, int ks, int s, int kk
         // the slab stores issued after them (two per k-step and group) stay in flight.
         // FDSRC: the next chunk of this full pass, whole, no biases (fdsrc = its source)
         const ChunkT c = (FD && LNERF_K16_FDSRC) ? ChunkT{fdsrc, KC_BYTES, -1} : chunk_at(a, ci + 1);
-        unsigned char* dst = ring + ((ci + 1) % R::slots) * R::slot_bytes;
+        // (the slot's LDS address: an integer add on the ring's, no pointer cast in the loop)
+        const unsigned dst = wc.ring + (unsigned)((ci + 1) % R::slots) * (unsigned)R::slot_bytes;
         int issued;
         if constexpr (spread) {
-            const int wave = wave_id();
-            const int woff = wave * 1024;
-            job.n = FD ? KP
-                       : (c.src && woff < c.bytes) ? (c.bytes - woff + NW * 1024 - 1) / (NW * 1024) : 0;
-            job.src = (const char*)c.src + woff;
-            job.dst = dst + woff;
+            job.n = FD ? KP : (c.src ? waddr::dma_piece_count(c.bytes, wc.wave, NW) : 0);
+            job.src = (const char*)c.src + wc.woff;
+            job.dst = dst + wc.woff;
+            job.lane16 = wc.lane16;
             // the biases of a first forward chunk: one more piece from the last wave, now
-            issued = job.n;
-            if (c.bias >= 0 && wave == NW - 1) {
-                glds16(a.b16 + (size_t)c.bias * 256 + lane * 4, lds_addr(bias_ring + (c.bias % 3) * 256));
-                ++issued;
-            }
+            issued = job.n + dma_bias<NW>(a, wc, c);
         } else {
-            issued = dma_chunk<NW>(a, c, dst, bias_ring);
+            issued = dma_chunk<NW>(a, wc, c, dst);
         }
         asm volatile("" ::: "memory");   // the slab stores stay younger than the pieces
         pending = issued ? 0 : -1;
     }
     if (st && pending >= 0) pending += 2 * NG;
-    const bool late = R::stagger && wave_id() >= 4;
+    const bool late = R::stagger && wc.wave >= 4;
     bf8 w[kDist + 1][3];
     read_tile<PL, 0>(base, w[0]);
     if constexpr (NTO > 1) read_tile<PL, 1>(base, w[1]);
@@ -663,9 +680,10 @@ __device__ __forceinline__ void k16_step(const K16Args& a, int ks, int s, int kk
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
             if constexpr (A24) {
-                store_slab_step24((unsigned char*)slab[q] + s * 3072, in[q][2 * s], in[q][2 * s + 1], ex[q]);
+                store_slab_step24(wc, (unsigned char*)slab[q] + waddr::slab_step_off_24(s), in[q][2 * s],
+                                  in[q][2 * s + 1], ex[q]);
             } else {
-                store_slab_step(slab[q] + s * 1024, in[q][2 * s], in[q][2 * s + 1]);
+                store_slab_step(wc, slab[q] + waddr::slab_step_off_f32(s) / 4, in[q][2 * s], in[q][2 * s + 1]);
             }
         }
     };
@@ -697,8 +715,10 @@ __device__ __forceinline__ void k16_step(const K16Args& a, int ks, int s, int kk
             asm volatile("" ::: "memory");
 #pragma unroll
             for (int q = 0; q < NG; ++q) {
-                if constexpr (A24) store_packed24((unsigned char*)slab[q] + s * 3072, f.pk[q]);
-                else store_slab_step(slab[q] + s * 1024, in[q][2 * s], in[q][2 * s + 1]);
+                if constexpr (A24)
+                    store_packed24(wc, (unsigned char*)slab[q] + waddr::slab_step_off_24(s), f.pk[q]);
+                else
+                    store_slab_step(wc, slab[q] + waddr::slab_step_off_f32(s) / 4, in[q][2 * s], in[q][2 * s + 1]);
             }
         }
         if (!late && last) dma_barrier(pending);
@@ -741,7 +761,7 @@ __device__ __forceinline__ void k16_step(const K16Args& a, int ks, int s, int kk
 // whole (KC NTO PL KiB = kPiecesMax pieces per wave), its DMA is issued without per-piece tests.
 template <int NTO, int PL, int NW, int NG, bool FULL, bool A24, int S>
 __device__ __forceinline__ void k16_pass_step(const K16Args& a, int ks, int& ci, unsigned char* ring,
-                                              float* bias_ring, const fx4 (&in)[NG][kMaxT], fx4 (&out)[NG][kMaxT],
+                                              const WaveCtx& wc, const fx4 (&in)[NG][kMaxT], fx4 (&out)[NG][kMaxT],
                                               float* const (&slab)[NG], const int (&ex)[NG], bf8 (&bh)[NG],
                                               bf8 (&bm)[NG], bf8 (&bl)[NG], int& pending,
                                               const unsigned short* pbase) {
@@ -757,17 +777,17 @@ __device__ __forceinline__ void k16_pass_step(const K16Args& a, int ks, int& ci,
         constexpr int fd = whole_next && kk == 0 ? 3 : 0;
         // the source of the chunk after this one (S / KC + 1 of the pass), for FDSRC
         const unsigned short* fdsrc = pbase + (size_t)(S / KC + 1) * (KC * NTO * PL * 512);
-        k16_step<NTO, PL, NW, NG, fd, A24>(a, FULL ? 8 : ks, S, kk, last, ci, ring, bias_ring, in, out, slab, ex,
+        k16_step<NTO, PL, NW, NG, fd, A24>(a, FULL ? 8 : ks, S, kk, last, ci, ring, wc, in, out, slab, ex,
                                            bh, bm, bl, pending, fdsrc);
     }
 }
 template <int NTO, int PL, int NW, int NG, bool FULL, bool A24, int... S>
 __device__ __forceinline__ void k16_pass_steps(std::integer_sequence<int, S...>, const K16Args& a, int ks, int& ci,
-                                               unsigned char* ring, float* bias_ring, const fx4 (&in)[NG][kMaxT],
+                                               unsigned char* ring, const WaveCtx& wc, const fx4 (&in)[NG][kMaxT],
                                                fx4 (&out)[NG][kMaxT], float* const (&slab)[NG], const int (&ex)[NG],
                                                bf8 (&bh)[NG], bf8 (&bm)[NG], bf8 (&bl)[NG], int& pending,
                                                const unsigned short* pbase) {
-    (k16_pass_step<NTO, PL, NW, NG, FULL, A24, S>(a, ks, ci, ring, bias_ring, in, out, slab, ex, bh, bm, bl, pending,
+    (k16_pass_step<NTO, PL, NW, NG, FULL, A24, S>(a, ks, ci, ring, wc, in, out, slab, ex, bh, bm, bl, pending,
                                                   pbase), ...);
 }
 
@@ -777,40 +797,40 @@ __device__ __forceinline__ void k16_pass_steps(std::integer_sequence<int, S...>,
 // pbase: the pass's first chunk in w16 (FULL passes with FDSRC; otherwise unused)
 template <int NTO, int PL, int NW, int NG, bool FULL = false, bool A24 = false>
 __device__ __forceinline__ void k16_pass(const K16Args& a, int ks, int& ci, unsigned char* ring,
-                                         float* bias_ring, const fx4 (&in)[NG][kMaxT], fx4 (&out)[NG][kMaxT],
+                                         const WaveCtx& wc, const fx4 (&in)[NG][kMaxT], fx4 (&out)[NG][kMaxT],
                                          float* const (&slab)[NG], const int (&ex)[NG],
                                          const unsigned short* pbase = nullptr) {
     bf8 bh[NG] = {}, bm[NG] = {}, bl[NG] = {};
 #pragma unroll
     for (int q = 0; q < NG; ++q) make_b<PL>(in[q], 0, ex[q], bh[q], bm[q], bl[q]);
     int pending = 0;
-    k16_pass_steps<NTO, PL, NW, NG, FULL, A24>(std::make_integer_sequence<int, 8>{}, a, ks, ci, ring, bias_ring, in,
+    k16_pass_steps<NTO, PL, NW, NG, FULL, A24>(std::make_integer_sequence<int, 8>{}, a, ks, ci, ring, wc, in,
                                                out, slab, ex, bh, bm, bl, pending, pbase);
 }
 // a hidden layer's pass: the FULL instantiation for 256-wide inputs (every hidden layer of cfg3)
 template <int HT, int PL, int NW, int NG, bool A24 = false>
 __device__ __forceinline__ void k16_hidden_pass(const K16Args& a, int ks, int& ci, unsigned char* ring,
-                                                float* bias_ring, const fx4 (&in)[NG][kMaxT], fx4 (&out)[NG][kMaxT],
+                                                const WaveCtx& wc, const fx4 (&in)[NG][kMaxT], fx4 (&out)[NG][kMaxT],
                                                 float* const (&slab)[NG], const int (&ex)[NG],
                                                 const unsigned short* pbase) {
     if constexpr (LNERF_K16_FULLDMA && HT == 16) {
         if (ks == 8) {
-            k16_pass<HT, PL, NW, NG, true, A24>(a, ks, ci, ring, bias_ring, in, out, slab, ex, pbase);
+            k16_pass<HT, PL, NW, NG, true, A24>(a, ks, ci, ring, wc, in, out, slab, ex, pbase);
             return;
         }
     }
-    k16_pass<HT, PL, NW, NG, false, A24>(a, ks, ci, ring, bias_ring, in, out, slab, ex);
+    k16_pass<HT, PL, NW, NG, false, A24>(a, ks, ci, ring, wc, in, out, slab, ex);
 }
 
 template <int PL, int NW, int NG>
 __device__ __forceinline__ void k16_pass_n(const K16Args& a, int ks, int& ci, unsigned char* ring,
-                                           float* bias_ring, int nto, const fx4 (&in)[NG][kMaxT],
+                                           const WaveCtx& wc, int nto, const fx4 (&in)[NG][kMaxT],
                                            fx4 (&out)[NG][kMaxT], float* const (&slab)[NG], const int (&ex)[NG]) {
-    if (nto <= 1) k16_pass<1, PL, NW, NG>(a, ks, ci, ring, bias_ring, in, out, slab, ex);
-    else if (nto <= 2) k16_pass<2, PL, NW, NG>(a, ks, ci, ring, bias_ring, in, out, slab, ex);
-    else if (nto <= 4) k16_pass<4, PL, NW, NG>(a, ks, ci, ring, bias_ring, in, out, slab, ex);
-    else if (nto <= 8) k16_pass<8, PL, NW, NG>(a, ks, ci, ring, bias_ring, in, out, slab, ex);
-    else k16_pass<16, PL, NW, NG>(a, ks, ci, ring, bias_ring, in, out, slab, ex);
+    if (nto <= 1) k16_pass<1, PL, NW, NG>(a, ks, ci, ring, wc, in, out, slab, ex);
+    else if (nto <= 2) k16_pass<2, PL, NW, NG>(a, ks, ci, ring, wc, in, out, slab, ex);
+    else if (nto <= 4) k16_pass<4, PL, NW, NG>(a, ks, ci, ring, wc, in, out, slab, ex);
+    else if (nto <= 8) k16_pass<8, PL, NW, NG>(a, ks, ci, ring, wc, in, out, slab, ex);
+    else k16_pass<16, PL, NW, NG>(a, ks, ci, ring, wc, in, out, slab, ex);
 }
 
 // The per-sample max|x| of a pass's input (lanes n, n + 16, n + 32, n + 48 hold sample n's
@@ -964,7 +984,9 @@ k16_fwd_bwd_kernel(K16Args a) {
     float* bias_ring = (float*)(lds + R::off_bias);
 
     if (a.gate && *a.gate == 0) return;   // the floor guard's re-run, not needed this step
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(), g = lane >> 4, n = lane & 15;
+    // the wave index, the rings' LDS addresses and the per-lane address constants, once
+    const WaveCtx wc = make_wave_ctx(ring, bias_ring);
+    const int tid = threadIdx.x, lane = tid & 63, wave = wc.wave, g = lane >> 4, n = lane & 15;
     const int wg = blockIdx.x;
     const int tile_samples = a.rpw * a.S;
 #if LNERF_K16_PRIO
@@ -1050,7 +1072,7 @@ k16_fwd_bwd_kernel(K16Args a) {
     __syncthreads();   // the first DMA overwrites the scratch
 
     int ci = 0;   // chunk stream position (chunk_at)
-    dma_chunk<NW>(a, chunk_at(a, 0), ring, bias_ring);
+    dma_chunk<NW>(a, wc, chunk_at(a, 0), wc.ring);
     dma_barrier(0);
     PROF_ADD(kPfPE, t_start);
     // ReLU mask bits of each group, per hidden layer: [L-1][logical wave][lane] u64
@@ -1078,7 +1100,7 @@ k16_fwd_bwd_kernel(K16Args a) {
         const float* bl = bias_ring + (l % 3) * 256 + g * 4;
         if (l < a.L - 1) {
             PROF_T(t_f);
-            k16_hidden_pass<HT, PL, NW, NG, a24_slabs(PL)>(a, a.ks_f[l], ci, ring, bias_ring, act, out, slab, ex,
+            k16_hidden_pass<HT, PL, NW, NG, a24_slabs(PL)>(a, a.ks_f[l], ci, ring, wc, act, out, slab, ex,
                                                            a.w16 + a.wf_off[l]);
             PROF_ADD(kPfFwd, t_f);
             PROF_T(t_fe);
@@ -1118,7 +1140,7 @@ k16_fwd_bwd_kernel(K16Args a) {
             }
             PROF_ADD(kPfFwdEpi, t_fe);
         } else {
-            k16_pass<1, PL, NW, NG, false, a24_slabs(PL)>(a, a.ks_f[l], ci, ring, bias_ring, act, out, slab, ex);
+            k16_pass<1, PL, NW, NG, false, a24_slabs(PL)>(a, a.ks_f[l], ci, ring, wc, act, out, slab, ex);
             fx4 bv[kMaxT];
             bias_read<1>(std::make_integer_sequence<int, 1>{}, bl, bv);
             // head pre-activations: features 0..3 = registers 0..3 of lane group 0; PL = 2 unscales
@@ -1189,7 +1211,7 @@ k16_fwd_bwd_kernel(K16Args a) {
             if (PL == 2 && l < a.L - 1) below |= valid[q] && gmin[q] + ex[q] <= kGuardExp;
             if (PL == 2 && l == a.L - 1) {
                 // the head: G's slab as it is (one k-step), then the pass on the column-scaled G row
-                store_slab_step(slab[q], act[q][0], act[q][1]);
+                store_slab_step(wc, slab[q], act[q][0], act[q][1]);
                 slab[q] = nullptr;
                 head_bscale(a, act[q]);
                 ex[q] = shift_of(sample_max<false>(act[q]));
@@ -1199,7 +1221,7 @@ k16_fwd_bwd_kernel(K16Args a) {
             }
             sh[q] = unscale(l, ex[q]);
         }
-        k16_hidden_pass<HT, PL, NW, NG>(a, a.ks_b[l], ci, ring, bias_ring, act, out, slab, ex, a.w16 + a.wb_off[l]);
+        k16_hidden_pass<HT, PL, NW, NG>(a, a.ks_b[l], ci, ring, wc, act, out, slab, ex, a.w16 + a.wb_off[l]);
         PROF_ADD(kPfBwd, t_b);
         PROF_T(t_be);
 #pragma unroll
@@ -1239,7 +1261,7 @@ k16_fwd_bwd_kernel(K16Args a) {
             g0s[q] = g0[q];
             if (PL == 2 && a.L == 1) {
                 // a head-only MLP: layer 0 is the head (its column-shifted planes, as above)
-                store_slab_step(g0[q], act[q][0], act[q][1]);
+                store_slab_step(wc, g0[q], act[q][0], act[q][1]);
                 g0s[q] = nullptr;
                 head_bscale(a, act[q]);
                 ex[q] = shift_of(sample_max<false>(act[q]));
@@ -1247,7 +1269,7 @@ k16_fwd_bwd_kernel(K16Args a) {
             }
             sh[q] = unscale(0, ex[q]);
         }
-        k16_pass_n<PL, NW, NG>(a, a.ks_b[0], ci, ring, bias_ring, a.to_b[0], act, out, g0s, ex);
+        k16_pass_n<PL, NW, NG>(a, a.ks_b[0], ci, ring, wc, a.to_b[0], act, out, g0s, ex);
 #pragma unroll
         for (int q = 0; q < NG; ++q) {
             if (valid[q]) {
@@ -1272,7 +1294,8 @@ k16_fwd_bwd_kernel(K16Args a) {
             if (PL == 2 && a.L > 1) below |= valid[q] && gmin[q] + shift_of(xm) <= kGuardExp;
 #pragma unroll
             for (int s = 0; s < 8; ++s)
-                if (s < a.ks_b[0]) store_slab_step(g0[q] + s * 1024, act[q][2 * s], act[q][2 * s + 1]);
+                if (s < a.ks_b[0])
+                    store_slab_step(wc, g0[q] + waddr::slab_step_off_f32(s) / 4, act[q][2 * s], act[q][2 * s + 1]);
         }
     }
     // one plain store per wave that met an element below the floor (every writer stores 1)

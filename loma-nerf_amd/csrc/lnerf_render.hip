@@ -20,6 +20,7 @@
 //    (k16_pack with one plane), the LDS-DMA ring and the chunk table are k16's.
 #include "lnerf_composite.h"
 #include "lnerf_internal.h"
+#include "lnerf_wave_addr.h"
 
 #include <stddef.h>
 #include <stdio.h>
@@ -128,18 +129,9 @@ __device__ __forceinline__ unsigned long long* kr_prof_slots() {
 #define KR_PROF_ADD(cat, t0)
 #endif
 
-__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
-
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-    return (unsigned)(size_t)(const __attribute__((address_space(3))) void*)p;
-}
-
-// One LDS-DMA wave instruction from inline asm, M0 written in the same statement (no register
-// destination; completion counted by the chunk barrier's vmcnt). As lnerf_k16.hip glds16.
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc),
-                 "s"(__builtin_amdgcn_readfirstlane(lds)));
-}
+// The LDS-DMA is lnerf_wave_addr.h's glds16s: one wave instruction from a scalar base plus the
+// lane's 16 B offset, M0 written in the same asm statement (no register destination; completion
+// counted by the chunk barrier's vmcnt).
 
 // feature of k-step s in element j of lane group g (k16's phi: the accumulator layout of the
 // previous layer is the B operand as it stands)
@@ -166,27 +158,28 @@ __device__ __forceinline__ Chunk chunk_at(const KrArgs& a, int ci) {
 // This wave's pieces of a chunk (1 KiB each, at byte wave * 1 KiB + p * 8 KiB), plus the bias
 // piece from the last wave.
 struct Job {
-    const char* src = nullptr;
-    unsigned char* dst = nullptr;
+    const char* src = nullptr;   // the wave's (uniform) address of piece 0: a scalar pair
+    unsigned dst = 0;            // LDS byte address of this wave's piece 0 (scalar)
     int n = 0;
+    unsigned lane16 = 0;         // WaveCtx::lane16, the only vector operand of a piece
 };
 
-__device__ __forceinline__ Job chunk_job(const KrArgs& a, int ci, unsigned char* ring, float* bias_ring) {
+__device__ __forceinline__ Job chunk_job(const KrArgs& a, const WaveCtx& wc, int ci) {
     const Chunk c = chunk_at(a, ci);
-    const int wave = wave_id(), lane = threadIdx.x & 63;
     Job j;
-    const int woff = wave * 1024;
-    j.n = (c.src && woff < c.bytes) ? (c.bytes - woff + kWaves * 1024 - 1) / (kWaves * 1024) : 0;
-    j.src = c.src + woff + lane * 16;
-    j.dst = ring + (ci % kSlots) * kSlot + woff;
-    if (c.bias >= 0 && wave == kWaves - 1)
-        glds16(a.b16 + (size_t)c.bias * 256 + lane * 4, lds_addr(bias_ring + (c.bias % 3) * 256));
+    j.n = c.src ? waddr::dma_piece_count(c.bytes, wc.wave, kWaves) : 0;
+    j.src = c.src + wc.woff;
+    j.dst = wc.ring + (unsigned)(ci % kSlots) * (unsigned)kSlot + wc.woff;
+    j.lane16 = wc.lane16;
+    if (c.bias >= 0 && wc.wave == kWaves - 1)
+        glds16s(a.b16 + (size_t)c.bias * 256, wc.lane16, wc.bias_ring + (unsigned)(c.bias % 3) * 1024u);
     return j;
 }
 
 template <int P>
 __device__ __forceinline__ void job_piece(const Job& j) {
-    if (P < j.n) glds16(j.src + P * (kWaves * 1024), lds_addr(j.dst + P * (kWaves * 1024)));
+    if (P < j.n)
+        glds16s_at<waddr::dma_piece_off(P, kWaves)>(j.src + waddr::dma_piece_off(P, kWaves), j.lane16, j.dst);
 }
 
 // the chunk the next k-step reads has landed (every DMA of this wave: vmcnt(0); the pass issues
@@ -251,13 +244,13 @@ __device__ __forceinline__ void kr_tiles_from(std::integer_sequence<int, O...>, 
 // k-step S of a pass (S < ks): chunk ci's sub-step S % 2; the first sub-step issues chunk ci + 1's
 // DMA, the last meets the barrier that waits for it.
 template <int NTO, int S>
-__device__ __forceinline__ void kr_step(const KrArgs& a, int ks, int& ci, unsigned char* ring, float* bias_ring,
+__device__ __forceinline__ void kr_step(const KrArgs& a, const WaveCtx& wc, int ks, int& ci, unsigned char* ring,
                                         const bf8 (&B)[kGroups][8], fx4 (&acc)[kGroups][kMaxT]) {
     if (S >= ks) return;
     constexpr int kk = S % kKC;
     const bool last = kk == kKC - 1 || S + 1 == ks;
     Job job;
-    if (kk == 0) job = chunk_job(a, ci + 1, ring, bias_ring);
+    if (kk == 0) job = chunk_job(a, wc, ci + 1);
     const int lane = threadIdx.x & 63;
     const unsigned char* base = ring + (ci % kSlots) * kSlot + kk * NTO * 1024 + lane * 16;
     bf8 w[kDist + 1];
@@ -266,7 +259,7 @@ __device__ __forceinline__ void kr_step(const KrArgs& a, int ks, int& ci, unsign
         if (o < NTO) w[o] = *(const bf8*)(base + o * 1024);
     // late waves: the barrier after the first half of the last k-step's tiles
     constexpr int H = NTO / 2;
-    const bool late = wave_id() >= 4;
+    const bool late = wc.wave >= 4;
     kr_tiles_from<NTO, 0>(std::make_integer_sequence<int, H>{}, base, w, B[0][S], B[1][S], acc, job);
     if (last && late) chunk_barrier();
     kr_tiles_from<NTO, H>(std::make_integer_sequence<int, NTO - H>{}, base, w, B[0][S], B[1][S], acc, job);
@@ -293,10 +286,10 @@ __device__ __forceinline__ void kr_head_resident(int ks, const unsigned char* he
 }
 
 template <int NTO, int... S>
-__device__ __forceinline__ void kr_pass(std::integer_sequence<int, S...>, const KrArgs& a, int ks, int& ci,
-                                        unsigned char* ring, float* bias_ring, const bf8 (&B)[kGroups][8],
+__device__ __forceinline__ void kr_pass(std::integer_sequence<int, S...>, const KrArgs& a, const WaveCtx& wc, int ks,
+                                        int& ci, unsigned char* ring, const bf8 (&B)[kGroups][8],
                                         fx4 (&acc)[kGroups][kMaxT]) {
-    (kr_step<NTO, S>(a, ks, ci, ring, bias_ring, B, acc), ...);
+    (kr_step<NTO, S>(a, wc, ks, ci, ring, B, acc), ...);
 }
 
 // Bias + ReLU of a hidden layer's accumulators into the next layer's bf16 B operands: tile o,
@@ -339,7 +332,9 @@ kr_fwd_kernel(KrArgs a) {
     float* comp = (float*)(lds + kOffComp);
     float* rayloss = (float*)(lds + kOffRay);
     float* bias_ring = (float*)(lds + kOffBias);
-    const int tid = threadIdx.x, lane = tid & 63, wave = wave_id(), g = lane >> 4, n = lane & 15;
+    // the wave index, the rings' LDS addresses and the lane's DMA offset, once
+    const WaveCtx wc = make_wave_ctx(ring, bias_ring);
+    const int tid = threadIdx.x, lane = tid & 63, wave = wc.wave, g = lane >> 4, n = lane & 15;
     const int wg = blockIdx.x;
     const int tile_samples = a.rpw * a.S;
 #if LNERF_PROF
@@ -351,15 +346,15 @@ kr_fwd_kernel(KrArgs a) {
     {
         // chunk 0 (layer 0's weights and biases) and the resident head, issued first: they land
         // while the encoding runs (waited for by the first chunk barrier)
-        const Job j0 = chunk_job(a, 0, ring, bias_ring);
+        const Job j0 = chunk_job(a, wc, 0);
         job_piece<0>(j0);
         job_piece<1>(j0);
         job_piece<2>(j0);
         job_piece<3>(j0);
         if (wave < a.ks[a.L - 1])
-            glds16((const char*)(a.w16 + a.head_off) + wave * 1024 + lane * 16, lds_addr(lds + kOffHead + wave * 1024));
+            glds16s((const char*)(a.w16 + a.head_off) + wc.woff, wc.lane16, wc.ring + kOffHead + wc.woff);
         if (wave == kWaves - 2)
-            glds16(a.b16 + (size_t)(a.L - 1) * 256 + lane * 4, lds_addr(lds + kOffHead + 8 * 1024));
+            glds16s(a.b16 + (size_t)(a.L - 1) * 256, wc.lane16, wc.ring + kOffHead + 8 * 1024);
     }
 
     // ---- layer-0 input (k0 <= 64: two k-steps) as bf16 B operands, group by group, through a
@@ -418,7 +413,7 @@ kr_fwd_kernel(KrArgs a) {
             for (int o = 0; o < kMaxT; ++o) acc[G][o] = fx4{0.0f, 0.0f, 0.0f, 0.0f};
         if (l < a.L - 1) {
             KR_PROF_T(t_p);
-            kr_pass<HT>(std::make_integer_sequence<int, 8>{}, a, ks, ci, ring, bias_ring, B, acc);
+            kr_pass<HT>(std::make_integer_sequence<int, 8>{}, a, wc, ks, ci, ring, B, acc);
             KR_PROF_ADD(kRpPass, t_p);
             KR_PROF_T(t_e);
             kr_epilogue<HT>(bl, acc, B);
