@@ -220,8 +220,10 @@ def _note(path, what, r):
 
 
 def check_against_f64(name, got, adj, prec, dx):
-    """got: run_vjp's result; the float64 reference takes the GPU's ReLU decisions when it has them."""
-    c = wl.case(name)
+    """got: run_vjp's result; the float64 reference takes the GPU's ReLU decisions when it has them.
+    name: a workload of render_vjp_workloads, or a Case of the caller's own."""
+    c = name if isinstance(name, wl.Case) else wl.case(name)
+    name = c.name
     w = c.w
     shapes = [x.shape for x in w.ws]
     masks = None
