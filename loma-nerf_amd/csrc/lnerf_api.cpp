@@ -208,6 +208,95 @@ LgAdjoints dev_adjoints(float* base, const Offsets& o, bool want_dx) {
     return a;
 }
 
+// The nested pointer tables of one side of a loma call: the primal arguments, or their adjoints (the
+// d_ arguments). The NeRF tables are null in an mlp_fit call.
+struct LomaTables {
+    float **x, ***ws, **bs, **target, ***io;
+    float ***rgba, **dists, **alpha, **cp, **wsamp, **acc;
+};
+
+// The adjoint tables into the staging block (the device accumulates into them) or back out of it.
+template <bool Out>
+void move_adjoints(float* h, const Offsets& o, const CallShape& c, const LomaTables& t, bool nerf, bool want_dx) {
+    const LgDims& d = c.d;
+    auto rect = [&](float** tab, size_t off, int rows, int cols, int ld) {
+        if (Out) scatter2(tab, h + off, rows, cols, ld);
+        else gather2(h + off, tab, rows, cols, ld);
+    };
+    if (want_dx) rect(t.x, o.dX, d.in_h, d.in_w, d.x_cols);
+    if (Out) scatter_w(t.ws, h + o.dW, c);
+    else gather_w(h + o.dW, t.ws, c);
+    if (Out) scatter_b(t.bs, h + o.dB, c);
+    else gather_b(h + o.dB, t.bs, c);
+    rect(t.target, o.dT, d.th, d.tw, d.t_cols);
+    if (Out) scatter_io(t.io, h + o.dIO, c);
+    else gather_io(h + o.dIO, t.io, c);
+    if (!nerf) return;
+    if (d.th > 0 && d.S > 0) {
+        if (Out) scatter3(t.rgba, h + o.drgba, d.th, d.S, 4);
+        else gather3(h + o.drgba, t.rgba, d.th, d.S, 4);
+        rect(t.dists, o.ddists, d.th, d.S, d.S);
+        rect(t.alpha, o.dalpha, d.th, d.S, d.S);
+        rect(t.cp, o.dcp, d.th, d.S, d.S);
+        rect(t.wsamp, o.dwsamp, d.th, d.S, d.S);
+    }
+    rect(t.acc, o.dacc, d.th, d.acc_cols, d.acc_cols);
+}
+
+// One compat call, nerf_evaluate_and_march (nerf) or mlp_fit, or with adj its grad_ form: the primal
+// tables (and the seed and the adjoint tables) gathered into the pinned block, uploaded, the loma-order
+// kernels run on the device block, what the call mutates downloaded and scattered back. A forward
+// call returns the loss.
+float stage_call(const char* what, bool nerf, const CallShape& c, const LomaTables& in, const LomaTables* adj,
+                 float seed) {
+    const LgDims& d = c.d;
+    const bool grad = adj != nullptr, S_ok = d.th > 0 && d.S > 0;
+    const Offsets o = carve(c, grad);
+    CompatCtx& cx = compat();
+    float* h = (float*)cx.host.get(o.total * sizeof(float));
+    float* g = (float*)cx.dev.get(o.total * sizeof(float));
+    std::memset(h, 0, o.total * sizeof(float));
+    // primal inputs (a grad call re-executes the forward on them; the rest is overwritten before use)
+    gather2(h + o.X, in.x, d.in_h, d.in_w, d.x_cols);
+    gather_w(h + o.W, in.ws, c);
+    gather_b(h + o.B, in.bs, c);
+    gather2(h + o.T, in.target, d.th, d.tw, d.t_cols);
+    gather_io(h + o.IO, in.io, c);
+    if (nerf) {
+        if (!grad || S_ok) gather2(h + o.dists, in.dists, d.th, d.S, d.S);
+        gather2(h + o.acc, in.acc, d.th, d.acc_cols, d.acc_cols);
+    }
+    const bool want_dx = grad && adj->x != nullptr;
+    if (grad) {
+        h[o.seed] = seed;
+        move_adjoints<false>(h, o, c, *adj, nerf, want_dx);
+    }
+    HIP_OK(hipMemcpyAsync(g, h, o.total * sizeof(float), hipMemcpyHostToDevice, cx.stream));
+    if (!grad) (nerf ? lg_nerf_forward : lg_mlp_fit_forward)(d, dev_buffers(g, o, false), g + o.loss, cx.stream);
+    else if (nerf) lg_nerf_grad(d, dev_buffers(g, o, true), dev_adjoints(g, o, want_dx), g + o.seed, cx.stream);
+    else lg_mlp_fit_grad(d, dev_buffers(g, o, true), dev_adjoints(g, o, want_dx), g + o.seed, cx.stream);
+    check_launch(what);
+    // forward: everything from IO to the loss is contiguous in the carve; grad: the adjoints end it
+    const size_t lo = grad ? o.dX : o.IO, hi = grad ? o.total : o.seed;
+    HIP_OK(hipMemcpyAsync(h + lo, g + lo, (hi - lo) * sizeof(float), hipMemcpyDeviceToHost, cx.stream));
+    HIP_OK(hipStreamSynchronize(cx.stream));
+    if (grad) {
+        move_adjoints<true>(h, o, c, *adj, nerf, want_dx);
+        return 0.0f;
+    }
+    scatter_io(in.io, h + o.IO, c);
+    if (nerf) {
+        if (S_ok) {
+            scatter3(in.rgba, h + o.rgba, d.th, d.S, 4);
+            scatter2(in.alpha, h + o.alpha, d.th, d.S, d.S);
+            scatter2(in.cp, h + o.cp, d.th, d.S, d.S);
+            scatter2(in.wsamp, h + o.wsamp, d.th, d.S, d.S);
+        }
+        scatter2(in.acc, h + o.acc, d.th, 3, d.acc_cols);
+    }
+    return h[o.loss];
+}
+
 template <class F>
 float guard_float(F&& f) {
     try {
@@ -246,38 +335,11 @@ extern "C" float nerf_evaluate_and_march(float** layer_input, int layer_input_h,
                                          float** weights_samples, float** accumulated_color) {
     (void)bias_shapes;  // never read by nerf.py
     return guard_float([&]() -> float {
-        CallShape c = make_shape(true, layer_input_h, layer_input_w, target_image_h, target_image_w,
-                                 num_weights, weight_shapes, intermediate_output_shapes, num_samples);
-        const LgDims& d = c.d;
-        Offsets o = carve(c, false);
-        CompatCtx& cx = compat();
-        float* h = (float*)cx.host.get(o.total * sizeof(float));
-        float* g = (float*)cx.dev.get(o.total * sizeof(float));
-        std::memset(h, 0, o.total * sizeof(float));
-        gather2(h + o.X, layer_input, d.in_h, d.in_w, d.x_cols);
-        gather_w(h + o.W, ws, c);
-        gather_b(h + o.B, bs, c);
-        gather2(h + o.T, target_image, d.th, d.tw, d.t_cols);
-        gather_io(h + o.IO, intermediate_outputs, c);
-        gather2(h + o.dists, dists, d.th, d.S, d.S);
-        gather2(h + o.acc, accumulated_color, d.th, d.acc_cols, d.acc_cols);
-        HIP_OK(hipMemcpyAsync(g, h, o.total * sizeof(float), hipMemcpyHostToDevice, cx.stream));
-        LgBuffers b = dev_buffers(g, o, false);
-        lg_nerf_forward(d, b, g + o.loss, cx.stream);
-        check_launch("nerf_evaluate_and_march");
-        // everything from IO to the loss is contiguous in the carve
-        HIP_OK(hipMemcpyAsync(h + o.IO, g + o.IO, (o.seed - o.IO) * sizeof(float),
-                              hipMemcpyDeviceToHost, cx.stream));
-        HIP_OK(hipStreamSynchronize(cx.stream));
-        scatter_io(intermediate_outputs, h + o.IO, c);
-        if (d.th > 0 && d.S > 0) {
-            scatter3(img_sample_rgba_arr, h + o.rgba, d.th, d.S, 4);
-            scatter2(alpha, h + o.alpha, d.th, d.S, d.S);
-            scatter2(cumprod_alpha, h + o.cp, d.th, d.S, d.S);
-            scatter2(weights_samples, h + o.wsamp, d.th, d.S, d.S);
-        }
-        scatter2(accumulated_color, h + o.acc, d.th, 3, d.acc_cols);
-        return h[o.loss];
+        const CallShape c = make_shape(true, layer_input_h, layer_input_w, target_image_h, target_image_w,
+                                       num_weights, weight_shapes, intermediate_output_shapes, num_samples);
+        const LomaTables in{layer_input, ws, bs, target_image, intermediate_outputs, img_sample_rgba_arr,
+                            dists, alpha, cumprod_alpha, weights_samples, accumulated_color};
+        return stage_call("nerf_evaluate_and_march", true, c, in, nullptr, 0.0f);
     });
 }
 
@@ -297,60 +359,15 @@ extern "C" void grad_nerf_evaluate_and_march(
     (void)d_layer_input_h; (void)d_layer_input_w; (void)d_target_image_h; (void)d_target_image_w;
     (void)d_num_weights; (void)d_weight_shapes; (void)d_bias_shapes;
     (void)d_intermediate_output_shapes; (void)d_num_samples; (void)bias_shapes;
-    (void)img_sample_rgba_arr; (void)alpha; (void)cumprod_alpha; (void)weights_samples;
     guard_int([&]() {
-        CallShape c = make_shape(true, layer_input_h, layer_input_w, target_image_h, target_image_w,
-                                 num_weights, weight_shapes, intermediate_output_shapes, num_samples);
-        const LgDims& d = c.d;
-        Offsets o = carve(c, true);
-        CompatCtx& cx = compat();
-        float* h = (float*)cx.host.get(o.total * sizeof(float));
-        float* g = (float*)cx.dev.get(o.total * sizeof(float));
-        std::memset(h, 0, o.total * sizeof(float));
-        const bool S_ok = d.th > 0 && d.S > 0;
-        // primal inputs the re-executed forward reads (the rest is overwritten before use)
-        gather2(h + o.X, layer_input, d.in_h, d.in_w, d.x_cols);
-        gather_w(h + o.W, ws, c);
-        gather_b(h + o.B, bs, c);
-        gather2(h + o.T, target_image, d.th, d.tw, d.t_cols);
-        gather_io(h + o.IO, intermediate_outputs, c);
-        if (S_ok) gather2(h + o.dists, dists, d.th, d.S, d.S);
-        gather2(h + o.acc, accumulated_color, d.th, d.acc_cols, d.acc_cols);
-        h[o.seed] = _dreturn;
-        // adjoints (accumulated into)
-        const bool want_dx = d_layer_input != nullptr;
-        if (want_dx) gather2(h + o.dX, d_layer_input, d.in_h, d.in_w, d.x_cols);
-        gather_w(h + o.dW, d_ws, c);
-        gather_b(h + o.dB, d_bs, c);
-        gather2(h + o.dT, d_target_image, d.th, d.tw, d.t_cols);
-        gather_io(h + o.dIO, d_intermediate_outputs, c);
-        if (S_ok) {
-            gather3(h + o.drgba, d_img_sample_rgba_arr, d.th, d.S, 4);
-            gather2(h + o.ddists, d_dists, d.th, d.S, d.S);
-            gather2(h + o.dalpha, d_alpha, d.th, d.S, d.S);
-            gather2(h + o.dcp, d_cumprod_alpha, d.th, d.S, d.S);
-            gather2(h + o.dwsamp, d_weights_samples, d.th, d.S, d.S);
-        }
-        gather2(h + o.dacc, d_accumulated_color, d.th, d.acc_cols, d.acc_cols);
-        HIP_OK(hipMemcpyAsync(g, h, o.total * sizeof(float), hipMemcpyHostToDevice, cx.stream));
-        lg_nerf_grad(d, dev_buffers(g, o, true), dev_adjoints(g, o, want_dx), g + o.seed, cx.stream);
-        check_launch("grad_nerf_evaluate_and_march");
-        HIP_OK(hipMemcpyAsync(h + o.dX, g + o.dX, (o.total - o.dX) * sizeof(float),
-                              hipMemcpyDeviceToHost, cx.stream));
-        HIP_OK(hipStreamSynchronize(cx.stream));
-        if (want_dx) scatter2(d_layer_input, h + o.dX, d.in_h, d.in_w, d.x_cols);
-        scatter_w(d_ws, h + o.dW, c);
-        scatter_b(d_bs, h + o.dB, c);
-        scatter2(d_target_image, h + o.dT, d.th, d.tw, d.t_cols);
-        scatter_io(d_intermediate_outputs, h + o.dIO, c);
-        if (S_ok) {
-            scatter3(d_img_sample_rgba_arr, h + o.drgba, d.th, d.S, 4);
-            scatter2(d_dists, h + o.ddists, d.th, d.S, d.S);
-            scatter2(d_alpha, h + o.dalpha, d.th, d.S, d.S);
-            scatter2(d_cumprod_alpha, h + o.dcp, d.th, d.S, d.S);
-            scatter2(d_weights_samples, h + o.dwsamp, d.th, d.S, d.S);
-        }
-        scatter2(d_accumulated_color, h + o.dacc, d.th, d.acc_cols, d.acc_cols);
+        const CallShape c = make_shape(true, layer_input_h, layer_input_w, target_image_h, target_image_w,
+                                       num_weights, weight_shapes, intermediate_output_shapes, num_samples);
+        // (of the primal tables the re-executed forward reads the inputs alone)
+        const LomaTables in{layer_input, ws, bs, target_image, intermediate_outputs, img_sample_rgba_arr,
+                            dists, alpha, cumprod_alpha, weights_samples, accumulated_color};
+        const LomaTables adj{d_layer_input, d_ws, d_bs, d_target_image, d_intermediate_outputs, d_img_sample_rgba_arr,
+                             d_dists, d_alpha, d_cumprod_alpha, d_weights_samples, d_accumulated_color};
+        stage_call("grad_nerf_evaluate_and_march", true, c, in, &adj, _dreturn);
     });
 }
 
@@ -362,27 +379,10 @@ extern "C" float mlp_fit(float** layer_input, int layer_input_h, int layer_input
     (void)layer_output;  // unused by mlp_fit.py
     (void)bias_shapes;
     return guard_float([&]() -> float {
-        CallShape c = make_shape(false, layer_input_h, layer_input_w, target_image_h, target_image_w,
-                                 num_weights, weight_shapes, intermediate_output_shapes, 0);
-        const LgDims& d = c.d;
-        Offsets o = carve(c, false);
-        CompatCtx& cx = compat();
-        float* h = (float*)cx.host.get(o.total * sizeof(float));
-        float* g = (float*)cx.dev.get(o.total * sizeof(float));
-        std::memset(h, 0, o.total * sizeof(float));
-        gather2(h + o.X, layer_input, d.in_h, d.in_w, d.x_cols);
-        gather_w(h + o.W, ws, c);
-        gather_b(h + o.B, bs, c);
-        gather2(h + o.T, target_image, d.th, d.tw, d.t_cols);
-        gather_io(h + o.IO, intermediate_outputs, c);
-        HIP_OK(hipMemcpyAsync(g, h, o.total * sizeof(float), hipMemcpyHostToDevice, cx.stream));
-        lg_mlp_fit_forward(d, dev_buffers(g, o, false), g + o.loss, cx.stream);
-        check_launch("mlp_fit");
-        HIP_OK(hipMemcpyAsync(h + o.IO, g + o.IO, (o.seed - o.IO) * sizeof(float),
-                              hipMemcpyDeviceToHost, cx.stream));
-        HIP_OK(hipStreamSynchronize(cx.stream));
-        scatter_io(intermediate_outputs, h + o.IO, c);
-        return h[o.loss];
+        const CallShape c = make_shape(false, layer_input_h, layer_input_w, target_image_h, target_image_w,
+                                       num_weights, weight_shapes, intermediate_output_shapes, 0);
+        const LomaTables in{layer_input, ws, bs, target_image, intermediate_outputs};
+        return stage_call("mlp_fit", false, c, in, nullptr, 0.0f);
     });
 }
 
@@ -401,37 +401,11 @@ extern "C" void grad_mlp_fit(float** layer_input, float** d_layer_input, int lay
     (void)d_target_image_h; (void)d_target_image_w; (void)d_num_weights; (void)d_weight_shapes;
     (void)bias_shapes; (void)d_bias_shapes; (void)d_intermediate_output_shapes;
     guard_int([&]() {
-        CallShape c = make_shape(false, layer_input_h, layer_input_w, target_image_h, target_image_w,
-                                 num_weights, weight_shapes, intermediate_output_shapes, 0);
-        const LgDims& d = c.d;
-        Offsets o = carve(c, true);
-        CompatCtx& cx = compat();
-        float* h = (float*)cx.host.get(o.total * sizeof(float));
-        float* g = (float*)cx.dev.get(o.total * sizeof(float));
-        std::memset(h, 0, o.total * sizeof(float));
-        gather2(h + o.X, layer_input, d.in_h, d.in_w, d.x_cols);
-        gather_w(h + o.W, ws, c);
-        gather_b(h + o.B, bs, c);
-        gather2(h + o.T, target_image, d.th, d.tw, d.t_cols);
-        gather_io(h + o.IO, intermediate_outputs, c);
-        h[o.seed] = _dreturn;
-        const bool want_dx = d_layer_input != nullptr;
-        if (want_dx) gather2(h + o.dX, d_layer_input, d.in_h, d.in_w, d.x_cols);
-        gather_w(h + o.dW, d_ws, c);
-        gather_b(h + o.dB, d_bs, c);
-        gather2(h + o.dT, d_target_image, d.th, d.tw, d.t_cols);
-        gather_io(h + o.dIO, d_intermediate_outputs, c);
-        HIP_OK(hipMemcpyAsync(g, h, o.total * sizeof(float), hipMemcpyHostToDevice, cx.stream));
-        lg_mlp_fit_grad(d, dev_buffers(g, o, true), dev_adjoints(g, o, want_dx), g + o.seed, cx.stream);
-        check_launch("grad_mlp_fit");
-        HIP_OK(hipMemcpyAsync(h + o.dX, g + o.dX, (o.total - o.dX) * sizeof(float),
-                              hipMemcpyDeviceToHost, cx.stream));
-        HIP_OK(hipStreamSynchronize(cx.stream));
-        if (want_dx) scatter2(d_layer_input, h + o.dX, d.in_h, d.in_w, d.x_cols);
-        scatter_w(d_ws, h + o.dW, c);
-        scatter_b(d_bs, h + o.dB, c);
-        scatter2(d_target_image, h + o.dT, d.th, d.tw, d.t_cols);
-        scatter_io(d_intermediate_outputs, h + o.dIO, c);
+        const CallShape c = make_shape(false, layer_input_h, layer_input_w, target_image_h, target_image_w,
+                                       num_weights, weight_shapes, intermediate_output_shapes, 0);
+        const LomaTables in{layer_input, ws, bs, target_image, intermediate_outputs};
+        const LomaTables adj{d_layer_input, d_ws, d_bs, d_target_image, d_intermediate_outputs};
+        stage_call("grad_mlp_fit", false, c, in, &adj, _dreturn);
     });
 }
 
@@ -476,16 +450,16 @@ struct lnerf_ctx {
     size_t ws_used = 0;  // lnerf_ctx_workspace_used
 };
 
-// The plan's carve (fused_plan_tile) against the bytes allocated for it (workspace_floats): the two are
-// written separately, and a plan that ran past the allocation would have its kernels write there.
+// The plan's carve against the bytes allocated for it: one carve (lnerf_plan.h) but two calls of it, the
+// plan's at its own tile and slab format, the allocation's at the larger of each.
 static size_t check_workspace(const FusedPlan& p, size_t bytes) {
     const size_t used = p.ws_floats * sizeof(float);
     if (used > bytes) fail("internal: the fused plan needs %zu workspace bytes, %zu were allocated", used, bytes);
     return used;
 }
 
-static int path_bits(const FusedPlan& p, bool train) {
-    return LNERF_PATH_FUSED | LNERF_PATH_K16 | (p.tile == 64 ? LNERF_PATH_K16_W4 : 0) |
+static int path_bits(const FusedPlan& p, bool train, bool kr = false) {
+    return LNERF_PATH_FUSED | LNERF_PATH_K16 | (p.tile == 64 ? LNERF_PATH_K16_W4 : 0) | (kr ? LNERF_PATH_KR : 0) |
            (train ? LNERF_PATH_DW16 : 0) | (train && a24_slabs(p.x6) ? LNERF_PATH_A24 : 0) | (p.x6 << 8);
 }
 
@@ -706,80 +680,137 @@ static bool use_fused(const lnerf_mlp& m, const lnerf_batch& b, int flags) {
     return ok;
 }
 
+// ---- the context entry points' shared steps (train step, render, render maps, their VJP) ----------
+static void validate_call(const lnerf_mlp* m, const lnerf_batch* b, int flags, const float* ws, const float* bs,
+                          bool need_target = true) {
+    validate(m, b, need_target);
+    validate_head(m, b, flags);
+    if (!ws || !bs) fail("null weights");
+}
+
+// LNERF_WANT_DINPUT: d_x in x's own layout. ENCODED input: that is LNERF_WANT_DX, on its code path.
+// POINTS / RAYS: the step writes the encoded gradient to the context's scratch and the input-gradient
+// kernel reverses it into the caller's d_x, which is returned (else NULL).
+static float* resolve_dinput(int& flags, const lnerf_batch& b, lnerf_outputs& o) {
+    if (flags & LNERF_WANT_DINPUT) {
+        if (b.input_mode == LNERF_INPUT_ENCODED) flags |= LNERF_WANT_DX;
+        else if (flags & LNERF_WANT_DX)
+            fail("LNERF_WANT_DX | LNERF_WANT_DINPUT needs ENCODED input (d_x cannot hold both layouts)");
+        else if (b.num_freqs > kMaxInputGradFreqs)
+            fail("LNERF_WANT_DINPUT runs at most %d frequencies", kMaxInputGradFreqs);
+    }
+    if (!(flags & (LNERF_WANT_DX | LNERF_WANT_DINPUT))) o.d_x = nullptr;
+    return (flags & LNERF_WANT_DX) ? nullptr : o.d_x;   // non-null: reverse the encoding
+}
+
+// A call's hold on its context, once its arguments have passed: the lock, the device, the stream. Any
+// failure from here on leaves the masks unreadable: the workspace they live in may be reallocated
+// before the call fails, and a render reuses it.
+struct CtxCall {
+    std::lock_guard<std::mutex> lock;
+    hipStream_t s;   // NULL: the device's default (null) stream
+    CtxCall(lnerf_ctx* ctx, void* stream) : lock(ctx->mu), s((hipStream_t)stream) {
+        ctx->last_k16_train = false;
+        ctx->ws_used = 0;
+        HIP_OK(hipSetDevice(ctx->device));
+    }
+};
+
+// What a call that ran leaves on the context. ev: the timing events it recorded, or NULL. train
+// (nullable): the fused training plan the masks, the guard word and the exceptional rows are read through.
+static hipEvent_t* timing_events(lnerf_ctx* ctx, int flags) { return (flags & LNERF_TIMING) ? ctx->ev : nullptr; }
+static void finish_call(lnerf_ctx* ctx, const hipEvent_t* ev, int path, const FusedPlan* train = nullptr) {
+    ctx->timed = ev != nullptr;
+    ctx->last_path = path;
+    if (train) {
+        ctx->last_plan = *train;
+        ctx->last_k16_train = true;
+    }
+}
+
+// A training call once its arguments have passed: lnerf_train_step, or with vjp lnerf_render_maps_vjp
+// (the same sequence seeded from the caller's adjoints; seed is 1 and the flags hold no LNERF_SEED_LOSS,
+// LNERF_K16_W4 or LNERF_HEAD_FIT then). d_input: resolve_dinput's.
+static void training_call(lnerf_ctx* ctx, const char* what, const lnerf_mlp& m, const float* ws, const float* bs,
+                          const lnerf_batch& b, float seed, int flags, lnerf_outputs o, float* d_input,
+                          const comp::VjpArgs* vjp, void* stream) {
+    const CtxCall call(ctx, stream);
+    const int vjp_bit = vjp ? LNERF_PATH_VJP : 0;
+    const bool fused = use_fused(m, b, flags);
+    if (d_input) o.d_x = (float*)ctx->dinput_ws.get((size_t)b.rays * b.samples * m.k[0] * sizeof(float));
+    if (!fused) {
+        generic_step(ctx, m, ws, bs, b, seed, flags, o, true, call.s, nullptr, vjp);
+        // (the generic reverse pass has seeded the encoded gradient already)
+        if (d_input) k_input_grad(b, o.d_x, nullptr, d_input, call.s);
+        finish_call(ctx, nullptr, LNERF_PATH_GENERIC | vjp_bit);
+        check_launch(what);
+        return;
+    }
+    const size_t bytes = fused_workspace_bytes(m, b.rays, b.samples, true, ctx->dw_grid);
+    void* wsb = ctx->fused_ws.get(bytes);
+    FusedPlan p{}, px{};
+    fused_plan(p, m, b, wsb, flags, true, ctx->dw_grid);
+    // the fp16x3 floor guard (lnerf_internal.h kGuardExp) under the default precision: the bf16x6 plan
+    // of the same step, run on the device only if k1 finds a hidden G element below fp16x3's floor (an
+    // explicit LNERF_MFMA_F16X3 asks for fp16x3 exactly; the mlp_fit head and the 64-sample workgroups
+    // have no bf16x6 k1)
+    const bool guarded = LNERF_GUARD && p.x6 == 2 && !(flags & (LNERF_MFMA_F16X3 | LNERF_K16_W4 | LNERF_HEAD_FIT));
+    if (guarded) {
+        fused_plan(px, m, b, wsb, flags | LNERF_MFMA_BF16X6, true, ctx->dw_grid);
+        px.guard = nullptr;
+        px.gate = p.guard;
+        px.w16 = p.w16x;   // packed by p's own pack launch, beside its fp16x3 planes
+        px.w16x = nullptr;
+        // (its fp32 activation slabs end the carve later than p's int24 ones)
+        ctx->ws_used = check_workspace(px, bytes);
+    } else {
+        ctx->ws_used = check_workspace(p, bytes);
+        p.guard = nullptr;
+        p.w16x = nullptr;
+    }
+    hipEvent_t* ev = timing_events(ctx, flags);
+    if (vjp) fused_render_vjp(p, ws, bs, b, flags, o, *vjp, call.s, ev, guarded ? &px : nullptr, d_input);
+    else fused_train_step(p, ws, bs, b, seed, flags, o, call.s, ev, guarded ? &px : nullptr, d_input);
+    check_launch(what);
+    finish_call(ctx, ev, path_bits(p, true) | vjp_bit, &p);
+}
+
+// A render once its arguments have passed: lnerf_render, or with maps lnerf_render_maps.
+static void render_call(lnerf_ctx* ctx, const char* what, const lnerf_mlp& m, const float* ws, const float* bs,
+                        const lnerf_batch& b, int flags, const lnerf_outputs& o, const comp::MapsArgs* maps,
+                        void* stream) {
+    const CtxCall call(ctx, stream);
+    const int maps_bit = maps ? LNERF_PATH_MAPS : 0;
+    flags &= ~(LNERF_WANT_DX | LNERF_WANT_DINPUT | LNERF_ACCUMULATE | LNERF_SEED_LOSS);   // a training call's
+    if (use_fused(m, b, flags)) {
+        const size_t bytes = fused_workspace_bytes(m, b.rays, b.samples, false, ctx->dw_grid);
+        FusedPlan p{};
+        fused_plan(p, m, b, ctx->fused_ws.get(bytes), flags, false, ctx->dw_grid);
+        ctx->ws_used = check_workspace(p, bytes);
+        p.guard = nullptr;   // (the floor guard is a training-step feature)
+        p.w16x = nullptr;
+        hipEvent_t* ev = timing_events(ctx, flags);
+        if (maps) fused_render_maps(p, ws, bs, b, o, *maps, call.s, flags, ev);
+        else fused_render(p, ws, bs, b, o, call.s, flags, ev);
+        finish_call(ctx, ev, path_bits(p, false, fused_render_uses_kr(p, flags)) | maps_bit);
+    } else {
+        generic_step(ctx, m, ws, bs, b, 1.0f, 0, o, false, call.s, maps);
+        finish_call(ctx, nullptr, LNERF_PATH_GENERIC | maps_bit);
+    }
+    check_launch(what);
+}
+
 extern "C" int lnerf_train_step(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* ws,
                                 const float* bs, const lnerf_batch* batch, float seed, int flags,
                                 const lnerf_outputs* out, void* stream) {
     return guard_int([&]() {
         if (!ctx) fail("null ctx");
-        validate(mlp, batch);
-        validate_head(mlp, batch, flags);
-        if (!ws || !bs) fail("null weights");
+        validate_call(mlp, batch, flags, ws, bs);
         lnerf_outputs o = out ? *out : lnerf_outputs{};
-        // LNERF_WANT_DINPUT: d_x in x's own layout. ENCODED input: that is LNERF_WANT_DX, on its code
-        // path. POINTS / RAYS: the step writes the encoded gradient to the context's scratch and the
-        // input-gradient kernel reverses it into the caller's d_x.
-        if (flags & LNERF_WANT_DINPUT) {
-            if (batch->input_mode == LNERF_INPUT_ENCODED) flags |= LNERF_WANT_DX;
-            else if (flags & LNERF_WANT_DX)
-                fail("LNERF_WANT_DX | LNERF_WANT_DINPUT needs ENCODED input (d_x cannot hold both layouts)");
-            else if (batch->num_freqs > kMaxInputGradFreqs)
-                fail("LNERF_WANT_DINPUT runs at most %d frequencies", kMaxInputGradFreqs);
-        }
-        if (!(flags & (LNERF_WANT_DX | LNERF_WANT_DINPUT))) o.d_x = nullptr;
-        float* d_input = (flags & LNERF_WANT_DX) ? nullptr : o.d_x;   // non-null: reverse the encoding
+        float* d_input = resolve_dinput(flags, *batch, o);
         if (flags & LNERF_HEAD_FIT) o.d_dists = nullptr;
         check_precision_flags(flags);
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        // any failure below leaves the masks unreadable: the workspace (mask_g) may be reallocated
-        // before the step fails
-        ctx->last_k16_train = false;
-        HIP_OK(hipSetDevice(ctx->device));
-        hipStream_t s = (hipStream_t)stream;   // NULL: the device's default (null) stream
-        const bool fused = use_fused(*mlp, *batch, flags);
-        if (d_input)
-            o.d_x = (float*)ctx->dinput_ws.get((size_t)batch->rays * batch->samples * mlp->k[0] * sizeof(float));
-        if (fused) {
-            const size_t bytes = fused_workspace_bytes(*mlp, batch->rays, batch->samples, true, ctx->dw_grid);
-            FusedPlan p{};
-            void* wsb = ctx->fused_ws.get(bytes);
-            fused_plan(p, *mlp, *batch, wsb, flags, true, ctx->dw_grid);
-            ctx->ws_used = 0;
-            // the fp16x3 floor guard (lnerf_internal.h kGuardExp) under the default precision: the
-            // bf16x6 plan of the same step, run on the device only if k1 finds a hidden G element
-            // below fp16x3's floor (an explicit LNERF_MFMA_F16X3 asks for fp16x3 exactly; the mlp_fit
-            // head and the 64-sample workgroups have no bf16x6 k1)
-            const bool guarded = LNERF_GUARD && p.x6 == 2 && !(flags & (LNERF_MFMA_F16X3 | LNERF_K16_W4 | LNERF_HEAD_FIT));
-            FusedPlan px{};
-            if (guarded) {
-                fused_plan(px, *mlp, *batch, wsb, flags | LNERF_MFMA_BF16X6, true, ctx->dw_grid);
-                px.guard = nullptr;
-                px.gate = p.guard;
-                px.w16 = p.w16x;   // packed by p's own pack launch, beside its fp16x3 planes
-                px.w16x = nullptr;
-                // (its fp32 activation slabs end the carve later than p's int24 ones)
-                ctx->ws_used = check_workspace(px, bytes);
-            } else {
-                ctx->ws_used = check_workspace(p, bytes);
-                p.guard = nullptr;
-                p.w16x = nullptr;
-            }
-            const bool timed = (flags & LNERF_TIMING) != 0;
-            fused_train_step(p, ws, bs, *batch, seed, flags, o, s, timed ? ctx->ev : nullptr, guarded ? &px : nullptr,
-                             d_input);
-            check_launch("lnerf_train_step");
-            ctx->timed = timed;
-            ctx->last_path = path_bits(p, true);
-            ctx->last_plan = p;
-            ctx->last_k16_train = true;
-        } else {
-            ctx->ws_used = 0;
-            generic_step(ctx, *mlp, ws, bs, *batch, seed, flags, o, true, s);
-            // (the generic reverse pass has seeded the encoded gradient already)
-            if (d_input) k_input_grad(*batch, o.d_x, nullptr, d_input, s);
-            ctx->timed = false;
-            ctx->last_path = LNERF_PATH_GENERIC;
-        }
-        check_launch("lnerf_train_step");
+        training_call(ctx, "lnerf_train_step", *mlp, ws, bs, *batch, seed, flags, o, d_input, nullptr, stream);
     });
 }
 
@@ -1141,33 +1172,10 @@ extern "C" int lnerf_render(lnerf_ctx* ctx, const lnerf_mlp* mlp, const float* w
                             void* stream) {
     return guard_int([&]() {
         if (!ctx) fail("null ctx");
-        validate(mlp, batch);
-        validate_head(mlp, batch, flags);
-        lnerf_outputs o = out ? *out : lnerf_outputs{};
+        validate_call(mlp, batch, flags, ws, bs);
+        const lnerf_outputs o = out ? *out : lnerf_outputs{};
         check_precision_flags(flags);
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        ctx->last_k16_train = false;   // a render reuses the workspace the masks live in
-        HIP_OK(hipSetDevice(ctx->device));
-        hipStream_t s = (hipStream_t)stream;   // NULL: the device's default (null) stream
-        if (use_fused(*mlp, *batch, flags & ~LNERF_WANT_DX)) {
-            const size_t bytes = fused_workspace_bytes(*mlp, batch->rays, batch->samples, false, ctx->dw_grid);
-            FusedPlan p{};
-            ctx->ws_used = 0;
-            fused_plan(p, *mlp, *batch, ctx->fused_ws.get(bytes), flags, false, ctx->dw_grid);
-            ctx->ws_used = check_workspace(p, bytes);
-            p.guard = nullptr;   // (the floor guard is a training-step feature)
-            p.w16x = nullptr;
-            const bool timed = (flags & LNERF_TIMING) != 0;
-            fused_render(p, ws, bs, *batch, o, s, flags, timed ? ctx->ev : nullptr);
-            ctx->timed = timed;
-            ctx->last_path = path_bits(p, false) | (fused_render_uses_kr(p, flags) ? LNERF_PATH_KR : 0);
-        } else {
-            ctx->timed = false;
-            ctx->ws_used = 0;
-            generic_step(ctx, *mlp, ws, bs, *batch, 1.0f, 0, o, false, s);
-            ctx->last_path = LNERF_PATH_GENERIC;
-        }
-        check_launch("lnerf_render");
+        render_call(ctx, "lnerf_render", *mlp, ws, bs, *batch, flags, o, nullptr, stream);
     });
 }
 
@@ -1177,9 +1185,7 @@ extern "C" int lnerf_render_maps(lnerf_ctx* ctx, const lnerf_mlp* mlp, const flo
     return guard_int([&]() {
         if (!ctx) fail("null ctx");
         if (flags & LNERF_HEAD_FIT) fail("lnerf_render_maps: LNERF_HEAD_FIT has no compositing to map");
-        validate(mlp, batch, false);
-        validate_head(mlp, batch, flags);
-        if (!ws || !bs) fail("null weights");
+        validate_call(mlp, batch, flags, ws, bs, false);
         const lnerf_render_outputs ro = out ? *out : lnerf_render_outputs{};
         if (!batch->target && ro.loss) fail("lnerf_render_maps: out->loss needs batch->target");
         if ((uintptr_t)ro.rgba % 16) fail("lnerf_render_maps: out->rgba must be 16-byte aligned (one store per sample)");
@@ -1193,31 +1199,7 @@ extern "C" int lnerf_render_maps(lnerf_ctx* ctx, const lnerf_mlp* mlp, const flo
         o.acc_color = ro.acc_color;
         comp::MapsArgs maps{ro.depth, ro.opacity, ro.weights, ro.rgba, sample_t};
         check_precision_flags(flags);
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        ctx->last_k16_train = false;   // a render reuses the workspace the masks live in
-        HIP_OK(hipSetDevice(ctx->device));
-        hipStream_t s = (hipStream_t)stream;   // NULL: the device's default (null) stream
-        const int rflags = flags & ~(LNERF_WANT_DX | LNERF_WANT_DINPUT | LNERF_ACCUMULATE | LNERF_SEED_LOSS);
-        if (use_fused(*mlp, *batch, rflags)) {
-            const size_t bytes = fused_workspace_bytes(*mlp, batch->rays, batch->samples, false, ctx->dw_grid);
-            FusedPlan p{};
-            ctx->ws_used = 0;
-            fused_plan(p, *mlp, *batch, ctx->fused_ws.get(bytes), rflags, false, ctx->dw_grid);
-            ctx->ws_used = check_workspace(p, bytes);
-            p.guard = nullptr;   // (the floor guard is a training-step feature)
-            p.w16x = nullptr;
-            const bool timed = (flags & LNERF_TIMING) != 0;
-            fused_render_maps(p, ws, bs, *batch, o, maps, s, rflags, timed ? ctx->ev : nullptr);
-            ctx->timed = timed;
-            ctx->last_path = path_bits(p, false) | (fused_render_uses_kr(p, rflags) ? LNERF_PATH_KR : 0) |
-                             LNERF_PATH_MAPS;
-        } else {
-            ctx->timed = false;
-            ctx->ws_used = 0;
-            generic_step(ctx, *mlp, ws, bs, *batch, 1.0f, 0, o, false, s, &maps);
-            ctx->last_path = LNERF_PATH_GENERIC | LNERF_PATH_MAPS;
-        }
-        check_launch("lnerf_render_maps");
+        render_call(ctx, "lnerf_render_maps", *mlp, ws, bs, *batch, flags, o, &maps, stream);
     });
 }
 
@@ -1231,9 +1213,7 @@ extern "C" int lnerf_render_maps_vjp(lnerf_ctx* ctx, const lnerf_mlp* mlp, const
         if (flags & kRefused)
             fail("lnerf_render_maps_vjp: flags 0x%x (LNERF_SEED_LOSS / LNERF_HEAD_FIT / LNERF_K16_W4 / "
                  "LNERF_RENDER_K16) have no meaning here", flags & kRefused);
-        validate(mlp, batch, false);
-        validate_head(mlp, batch, flags);
-        if (!ws || !bs) fail("null weights");
+        validate_call(mlp, batch, flags, ws, bs, false);
         if (!adj) fail("lnerf_render_maps_vjp: null adjoints");
         const comp::VjpArgs vjp{adj->d_acc_color, adj->d_depth, adj->d_opacity, adj->d_weights, adj->d_rgba, sample_t};
         if (!vjp.d_acc_color && !vjp.d_depth && !vjp.d_opacity && !vjp.d_weights && !vjp.d_rgba)
@@ -1247,62 +1227,9 @@ extern "C" int lnerf_render_maps_vjp(lnerf_ctx* ctx, const lnerf_mlp* mlp, const
         lnerf_outputs o = out ? *out : lnerf_outputs{};
         if (o.loss || o.d_target)
             fail("lnerf_render_maps_vjp: out->loss and out->d_target must be NULL (there is no loss and no target)");
-        // d_x as lnerf_train_step forms it (LNERF_WANT_DX / LNERF_WANT_DINPUT)
-        if (flags & LNERF_WANT_DINPUT) {
-            if (batch->input_mode == LNERF_INPUT_ENCODED) flags |= LNERF_WANT_DX;
-            else if (flags & LNERF_WANT_DX)
-                fail("LNERF_WANT_DX | LNERF_WANT_DINPUT needs ENCODED input (d_x cannot hold both layouts)");
-            else if (batch->num_freqs > kMaxInputGradFreqs)
-                fail("LNERF_WANT_DINPUT runs at most %d frequencies", kMaxInputGradFreqs);
-        }
-        if (!(flags & (LNERF_WANT_DX | LNERF_WANT_DINPUT))) o.d_x = nullptr;
-        float* d_input = (flags & LNERF_WANT_DX) ? nullptr : o.d_x;   // non-null: reverse the encoding
+        float* d_input = resolve_dinput(flags, *batch, o);   // d_x as lnerf_train_step forms it
         check_precision_flags(flags);
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        ctx->last_k16_train = false;
-        HIP_OK(hipSetDevice(ctx->device));
-        hipStream_t s = (hipStream_t)stream;   // NULL: the device's default (null) stream
-        const bool fused = use_fused(*mlp, *batch, flags);
-        if (!fused && (flags & LNERF_ACCUMULATE)) fail("LNERF_ACCUMULATE is only supported on the fused path");
-        if (d_input)
-            o.d_x = (float*)ctx->dinput_ws.get((size_t)batch->rays * batch->samples * mlp->k[0] * sizeof(float));
-        if (fused) {
-            const size_t bytes = fused_workspace_bytes(*mlp, batch->rays, batch->samples, true, ctx->dw_grid);
-            FusedPlan p{};
-            void* wsb = ctx->fused_ws.get(bytes);
-            fused_plan(p, *mlp, *batch, wsb, flags, true, ctx->dw_grid);
-            ctx->ws_used = 0;
-            // the fp16x3 floor guard under the default precision, as in lnerf_train_step
-            const bool guarded = LNERF_GUARD && p.x6 == 2 && !(flags & LNERF_MFMA_F16X3);
-            FusedPlan px{};
-            if (guarded) {
-                fused_plan(px, *mlp, *batch, wsb, flags | LNERF_MFMA_BF16X6, true, ctx->dw_grid);
-                px.guard = nullptr;
-                px.gate = p.guard;
-                px.w16 = p.w16x;
-                px.w16x = nullptr;
-                ctx->ws_used = check_workspace(px, bytes);
-            } else {
-                ctx->ws_used = check_workspace(p, bytes);
-                p.guard = nullptr;
-                p.w16x = nullptr;
-            }
-            const bool timed = (flags & LNERF_TIMING) != 0;
-            fused_render_vjp(p, ws, bs, *batch, flags, o, vjp, s, timed ? ctx->ev : nullptr, guarded ? &px : nullptr,
-                             d_input);
-            check_launch("lnerf_render_maps_vjp");
-            ctx->timed = timed;
-            ctx->last_path = path_bits(p, true) | LNERF_PATH_VJP;
-            ctx->last_plan = p;
-            ctx->last_k16_train = true;
-        } else {
-            ctx->ws_used = 0;
-            generic_step(ctx, *mlp, ws, bs, *batch, 1.0f, flags, o, true, s, nullptr, &vjp);
-            if (d_input) k_input_grad(*batch, o.d_x, nullptr, d_input, s);
-            ctx->timed = false;
-            ctx->last_path = LNERF_PATH_GENERIC | LNERF_PATH_VJP;
-        }
-        check_launch("lnerf_render_maps_vjp");
+        training_call(ctx, "lnerf_render_maps_vjp", *mlp, ws, bs, *batch, 1.0f, flags, o, d_input, &vjp, stream);
     });
 }
 

@@ -1,5 +1,6 @@
-// lnerf_fused.hip -- the throughput path's plan and orchestration: the workspace layout, the
-// reductions, and the kernel sequence of one fused training step or render.
+// lnerf_fused.hip -- the throughput path's plan and orchestration: the plan's device pointers (the
+// layout and the workspace carve are lnerf_plan.h's), the reductions, and the kernel sequences of a
+// fused training step and of a render.
 //
 // Hot path of the reference: scripts/nerf.py:1-304 (forward) and its rev_diff (:306), called per
 // chunk from train_nerf.py:325/395. Here one step handles the whole batch:
@@ -21,13 +22,9 @@
 // (LNERF_GENERIC).
 #include "lnerf_internal.h"
 
-#include <stdio.h>
-
 namespace lnerf {
 
 namespace {
-
-constexpr int kTileSamples = 128;   // samples per k16 workgroup (8 waves x 16); 64 with K16_W4
 
 // ---------------------------------------------------------------------------------------------
 // reductions
@@ -56,7 +53,6 @@ __global__ void __launch_bounds__(256) loss_reduce_kernel(const float* __restric
 // 320 000 partials of a config-5 frame serially took 0.285 ms): block b sums the contiguous range
 // [b per, (b + 1) per) of the partials by the same strided-then-tree order, into stage[b];
 // loss_reduce_kernel then sums the kLossStage1 block sums. Fixed grid, fixed order: deterministic.
-constexpr int kLossStage1 = 256;
 __global__ void __launch_bounds__(256) loss_stage1_kernel(const float* __restrict__ part, int n, int per,
                                                           float* __restrict__ stage) {
     __shared__ float red[256];
@@ -137,89 +133,6 @@ __global__ void grad_reduce_kernel(ReduceArgs a) {
     }
 }
 
-constexpr size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline int pow2_16(int t) { return t <= 1 ? 1 : t <= 2 ? 2 : t <= 4 ? 4 : t <= 8 ? 8 : 16; }
-
-// Sizes and offsets of one step's workspace (floats unless noted).
-struct Layout {
-    int ht16, ks16_f[kMaxLayers], ks16_b[kMaxLayers], to16_f[kMaxLayers], to16_b[kMaxLayers];
-    size_t w16f_off[kMaxLayers], w16b_off[kMaxLayers], w16_total;   // u16
-    size_t b16_total;
-    size_t mask_total;                                               // u64
-    size_t act_off[kMaxLayers], x_off, act_total;
-    size_t grad_off[kMaxLayers], grad_total;
-    int splits[kMaxLayers], wg_off[kMaxLayers], dw_grid;
-    size_t dwp_off[kMaxLayers], dwp_total, dbp_off[kMaxLayers], dbp_total;
-    int num_wg, blocks, rpw;
-};
-
-// train = false (render): no slabs, masks or dW partials (the forward-only kernel writes none).
-// a_tile: float slots per 32 x 32 tile-block of an activation slab (a_tile_floats: 768 for int24 A
-// slabs, 1024 for fp32; the workspace is sized with 1024)
-void make_layout(Layout& y, const lnerf_mlp& m, int rays, int S, bool train, int dw_grid, int tile,
-                 int a_tile = 1024) {
-    const int L = m.num_layers;
-    int kt[kMaxLayers], nt[kMaxLayers];
-    for (int l = 0; l < L; ++l) {
-        kt[l] = (m.k[l] + 31) / 32;
-        nt[l] = (m.n[l] + 31) / 32;
-    }
-    // k16 packing: every hidden layer's forward and every l >= 1 backward with ht16 16-wide output
-    // tiles, the head forward with 1 and the dX pass with pow2(k0 / 16); per layer and pass, 3
-    // planes of [k-step][output tile][1 KiB] (sized for bf16x6; fp16x3 / bf16 use 2 / 1)
-    int mx16 = 1;
-    for (int l = 0; l + 1 < L; ++l) mx16 = (m.n[l] + 15) / 16 > mx16 ? (m.n[l] + 15) / 16 : mx16;
-    y.ht16 = pow2_16(mx16);
-    size_t off = 0;
-    for (int l = 0; l < L; ++l) {
-        y.ks16_f[l] = kt[l];
-        y.ks16_b[l] = nt[l];
-        y.to16_f[l] = (l < L - 1) ? y.ht16 : 1;
-        y.to16_b[l] = (l >= 1) ? y.ht16 : pow2_16((m.k[0] + 15) / 16);
-        y.w16f_off[l] = off; off += align_up((size_t)y.ks16_f[l] * y.to16_f[l] * 3 * 512, 512);
-        y.w16b_off[l] = off; off += align_up((size_t)y.ks16_b[l] * y.to16_b[l] * 3 * 512, 512);
-    }
-    y.w16_total = off;
-    y.b16_total = (size_t)L * 256;
-    y.rpw = S >= tile ? 1 : tile / S;
-    y.num_wg = (rays + y.rpw - 1) / y.rpw;
-    y.mask_total = train ? (size_t)y.num_wg * (L > 1 ? L - 1 : 0) * (tile / 16) * 64 : 0;
-    y.blocks = y.num_wg * (tile / 32);
-    off = 0;
-    y.x_off = off; off += (size_t)y.blocks * kt[0] * a_tile;
-    for (int l = 0; l < L - 1; ++l) { y.act_off[l] = off; off += (size_t)y.blocks * nt[l] * a_tile; }
-    y.act_total = train ? off : 0;
-    off = 0;
-    for (int l = 0; l < L; ++l) { y.grad_off[l] = off; off += (size_t)y.blocks * nt[l] * 1024; }
-    y.grad_total = train ? off : 0;
-    // dW: one launch over every layer, ~dw_grid workgroups (lnerf_ctx_set_option
-    // LNERF_OPT_DW_GRID; 512 by default) split between the layers in proportion to the slab bytes
-    // each one streams (kt + nt tiles per 32-sample block): the kernel is bandwidth-bound, so
-    // equal bytes per workgroup balance it. One partial per split.
-    const int grid = dw_grid > 0 ? (dw_grid < 16 ? 16 : dw_grid > 4096 ? 4096 : dw_grid)
-                                 : default_dw_grid((long long)rays * S);
-    auto weight = [&](int l) { return kt[l] + nt[l]; };
-    int tiles_sum = 0;
-    for (int l = 0; l < L; ++l) tiles_sum += weight(l);
-    size_t dwp = 0, dbp = 0;
-    int wg = 0;
-    for (int l = 0; l < L; ++l) {
-        int sp = (int)((long long)grid * weight(l) / tiles_sum);
-        sp = sp < 1 ? 1 : sp;
-        sp = sp > y.blocks ? y.blocks : sp;
-        y.splits[l] = sp;
-        y.wg_off[l] = wg;
-        wg += sp;
-        y.dwp_off[l] = dwp;
-        dwp += (size_t)sp * kt[l] * 32 * nt[l] * 32;
-        y.dbp_off[l] = dbp;
-        dbp += (size_t)sp * nt[l] * 32;
-    }
-    y.dw_grid = wg;
-    y.dwp_total = train ? dwp : 0;
-    y.dbp_total = train ? dbp : 0;
-}
-
 }  // namespace
 
 bool fused_supported(const lnerf_mlp& m, int rays, int S, int input_mode, const char** why, bool head_fit) {
@@ -242,28 +155,9 @@ bool fused_supported(const lnerf_mlp& m, int rays, int S, int input_mode, const 
     return w == nullptr;
 }
 
-static size_t workspace_floats(const lnerf_mlp& m, int rays, int S, bool train, int dw_grid, int tile) {
-    Layout y;
-    make_layout(y, m, rays, S, train, dw_grid, tile);
-    return 64 + align_up(y.act_total, 64) + align_up(y.grad_total, 64) + align_up((size_t)y.num_wg, 64) +
-           align_up(y.dwp_total, 64) + align_up(y.dbp_total, 64) + 64 + align_up((size_t)kLossStage1, 64) +
-           2 * align_up((y.w16_total + 1) / 2, 64) +   // + the guard's bf16x6 planes
-           align_up(y.b16_total, 64) + align_up(y.mask_total * 2, 64) + 64 +   // + the fp16x3 shifts
-           align_up((size_t)kMaxLayers * kWmaxParts + kWmaxParts * kHeadCols, 64) +   // per-block max|W|
-           align_up((size_t)kHeadCols, 64) +                                     // head column max|W|
-           (train ? align_up((size_t)m.num_layers * y.num_wg * tile, 64) +      // per-sample words
-                        align_up((size_t)m.num_layers * y.num_wg * 8, 64) +         // per-wave minima
-                        align_up((size_t)2 * y.dw_grid, 64) : 0);                   // exceptional rows
-}
-
-// Either tile size (fused_plan runs 64 under LNERF_K16_W4, 128 otherwise).
+// Sized for either tile size and fp32 activation slabs, whichever plan then runs (lnerf_plan.h).
 size_t fused_workspace_bytes(const lnerf_mlp& m, int rays, int S, bool train, int dw_grid) {
-    size_t f = workspace_floats(m, rays, S, train, dw_grid, kTileSamples);
-    if (S <= 64) {
-        const size_t f64 = workspace_floats(m, rays, S, train, dw_grid, 64);
-        f = f64 > f ? f64 : f;
-    }
-    return f * sizeof(float);
+    return fused_workspace_floats(m, rays, S, train, dw_grid) * sizeof(float);
 }
 
 static void fused_plan_tile(FusedPlan& p, const lnerf_mlp& m, const lnerf_batch& b, void* ws_base, int flags,
@@ -306,57 +200,48 @@ static void fused_plan_tile(FusedPlan& p, const lnerf_mlp& m, const lnerf_batch&
     p.F = b.num_freqs;
     p.dw_grid = y.dw_grid;
     p.x_off = y.x_off;
+    // the carve (lnerf_plan.h fused_carve): act last, so that the fp16x3 plan and its bf16x6 re-run
+    // (the floor guard) share every other pointer
+    const FusedCarve c = fused_carve(y, p.L, tile, train);
     float* base = (float*)ws_base;
-    size_t off = 0;
-    auto take = [&](size_t floats) {
-        float* q = base + off;
-        off += align_up(floats, 64);
-        return q;
-    };
-    // every region but the activation slabs (whose size follows the split: a_tile_floats) first, so
-    // that the fp16x3 plan and its bf16x6 re-run (the floor guard) share all other pointers
-    p.guard = (int*)take(64);
-    p.grad = take(y.grad_total);
-    p.loss_part = take((size_t)y.num_wg);
-    p.dw_part = take(y.dwp_total);
-    p.db_part = take(y.dbp_total);
-    p.loss_total = take(1);
-    p.loss_stage = take(kLossStage1);
-    p.w16 = (unsigned short*)take((y.w16_total + 1) / 2);
-    p.w16x = (unsigned short*)take((y.w16_total + 1) / 2);
-    p.b16 = take(y.b16_total);
-    p.mask_g = (unsigned long long*)take(y.mask_total * 2);
-    p.wexp16 = (int*)take(2 * kMaxLayers);
+    p.guard = (int*)(base + c.guard);
+    p.grad = base + c.grad;
+    p.loss_part = base + c.loss_part;
+    p.dw_part = base + c.dw_part;
+    p.db_part = base + c.db_part;
+    p.loss_total = base + c.loss_total;
+    p.loss_stage = base + c.loss_stage;
+    p.w16 = (unsigned short*)(base + c.w16);
+    p.w16x = (unsigned short*)(base + c.w16x);
+    p.b16 = base + c.b16;
+    p.mask_g = (unsigned long long*)(base + c.mask_g);
+    p.wexp16 = (int*)(base + c.wexp16);
     p.dw_shift = p.wexp16 + kMaxLayers;
-    p.wmax_part = (int*)take((size_t)kMaxLayers * kWmaxParts + kWmaxParts * kHeadCols);
-    p.hexp16 = (int*)take((size_t)kHeadCols);
-    p.sexp = (unsigned*)(base + off);                                // L x num_wg x tile words
-    if (train) off += align_up((size_t)p.L * y.num_wg * tile, 64);
-    p.epart = (int*)(base + off);
-    if (train) off += align_up((size_t)p.L * y.num_wg * 8, 64);
-    p.xcount = (int*)(base + off);
-    if (train) off += align_up((size_t)2 * y.dw_grid, 64);
-    p.act = take(y.act_total);
-    p.ws_floats = off;   // the callers hold this against what they allocated (workspace_floats)
+    p.wmax_part = (int*)(base + c.wmax_part);
+    p.hexp16 = (int*)(base + c.hexp16);
+    p.sexp = (unsigned*)(base + c.sexp);
+    p.epart = (int*)(base + c.epart);
+    p.xcount = (int*)(base + c.xcount);
+    p.act = base + c.act;
+    p.ws_floats = c.total;   // the callers hold this against what they allocated (fused_workspace_bytes)
 }
 
 void fused_plan(FusedPlan& p, const lnerf_mlp& m, const lnerf_batch& b, void* ws_base, int flags, bool train,
                 int dw_grid) {
-    if (flags & LNERF_K16_W4) {
+    const int tile = (flags & LNERF_K16_W4) ? 64 : kTileSamples;
+    if (tile == 64) {
         // k16 on 4-wave, 64-sample workgroups (two per CU): whole rays must fit 64 samples and the
         // ring 80 KiB (fp16x3 / plain bf16). Measured slower than the 8-wave workgroup at cfg3
         // (the second workgroup doubles the weight stream's LDS-DMA). An explicit
         // request that cannot run is an error, never a silent fall-back.
         if (flags & LNERF_MFMA_BF16X6) marshal::fail("LNERF_K16_W4 does not run the bf16x6 split (its ring needs 96 KiB)");
         if (b.samples > 64) marshal::fail("LNERF_K16_W4 needs samples <= 64 (whole rays in a 64-sample tile)");
-        fused_plan_tile(p, m, b, ws_base, flags, train, dw_grid, 64);
-    } else {
-        fused_plan_tile(p, m, b, ws_base, flags, train, dw_grid, kTileSamples);
     }
+    fused_plan_tile(p, m, b, ws_base, flags, train, dw_grid, tile);
     p.head_fit = (flags & LNERF_HEAD_FIT) ? 1 : 0;
 }
 
-static ReduceArgs reduce_args(const FusedPlan& p, const lnerf_outputs& out, int flags) {
+static ReduceArgs reduce_args(const FusedPlan& p, const lnerf_outputs& out, const float* scale, bool accumulate) {
     ReduceArgs ra{};
     ra.L = p.L;
     for (int l = 0; l < p.L; ++l) {
@@ -374,26 +259,37 @@ static ReduceArgs reduce_args(const FusedPlan& p, const lnerf_outputs& out, int 
     ra.db_part = p.db_part;
     ra.d_ws = out.d_ws;
     ra.d_bs = out.d_bs;
-    ra.scale = (flags & LNERF_SEED_LOSS) ? p.loss_total : nullptr;
-    ra.accumulate = (flags & LNERF_ACCUMULATE) ? 1 : 0;
+    ra.scale = scale;
+    ra.accumulate = accumulate ? 1 : 0;
     return ra;
 }
 
-void fused_train_step(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b, float seed,
-                      int flags, const lnerf_outputs& out, hipStream_t s, hipEvent_t* ev, const FusedPlan* px,
-                      float* d_input) {
-    const bool seed_loss = (flags & LNERF_SEED_LOSS) != 0;
-    auto mark = [&](int i) {
+// The event marks between a sequence's kernels (LNERF_TIMING); ev is nullable.
+struct Marks {
+    hipEvent_t* ev;
+    hipStream_t s;
+    void operator()(int i) const {
         if (ev) (void)hipEventRecord(ev[i], s);
-    };
+    }
+};
+
+// The training sequence: pack, k1, k1-reduce, dW, the gated re-run, the dW/db reduce, the input
+// gradient. k1(plan) launches the step's k1 instantiation on a plan; loss (nullable) is where
+// k1_reduce leaves the batch loss; scale (nullable: LNERF_SEED_LOSS, the device loss) multiplies
+// every gradient after the fact.
+template <class K1>
+static void train_sequence(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b,
+                           const lnerf_outputs& out, const K1& k1, float* loss, const float* scale, bool accumulate,
+                           hipStream_t s, hipEvent_t* ev, const FusedPlan* px, float* d_input) {
+    const Marks mark{ev, s};
     const size_t nred = (size_t)p.L * p.w_k * p.w_n + (size_t)p.L * p.w_n;
     const unsigned rgrid = (unsigned)((nred + 255) / 256);
     mark(0);
     k16_pack(p, ws, bs, s);
     mark(1);
-    k16_launch(p, b, seed_loss ? 1.0f : seed, out, true, s);
+    k1(p);
     mark(2);
-    k1_reduce_launch(p, out.loss, s);
+    k1_reduce_launch(p, loss, s);
     mark(3);
     dw16_launch(p, s);
     mark(4);
@@ -403,54 +299,40 @@ void fused_train_step(const FusedPlan& p, const float* ws, const float* bs, cons
         // included), each kernel exiting at once while k1 left the guard clear; the one reduction
         // below then sums whichever partials the last dW kernel wrote
         // (px's bf16x6 planes came out of p's pack: k16_pack wrote both formats)
-        k16_launch(*px, b, seed_loss ? 1.0f : seed, out, true, s);
-        k1_reduce_launch(*px, out.loss, s);
+        k1(*px);
+        k1_reduce_launch(*px, loss, s);
         dw16_launch(*px, s);
     }
-    const ReduceArgs ra = reduce_args(p, out, flags);
-    grad_reduce_kernel<<<rgrid, 256, 0, s>>>(ra);
-    if (seed_loss) {
-        if (out.d_dists) k_scale_by_scalar(out.d_dists, (size_t)p.R, p.loss_total, s);
+    grad_reduce_kernel<<<rgrid, 256, 0, s>>>(reduce_args(p, out, scale, accumulate));
+    if (scale) {
+        if (out.d_dists) k_scale_by_scalar(out.d_dists, (size_t)p.R, scale, s);
         if (out.d_target)
-            k_scale_by_scalar(out.d_target, (size_t)p.rays * (p.head_fit ? p.n[p.L - 1] : 3), p.loss_total, s);
-        if (out.d_x && !d_input) k_scale_by_scalar(out.d_x, (size_t)p.R * p.k[0], p.loss_total, s);
+            k_scale_by_scalar(out.d_target, (size_t)p.rays * (p.head_fit ? p.n[p.L - 1] : 3), scale, s);
+        if (out.d_x && !d_input) k_scale_by_scalar(out.d_x, (size_t)p.R * p.k[0], scale, s);
     }
     // LNERF_WANT_DINPUT (POINTS / RAYS): out.d_x is the scratch k1 -- or the guard's re-run -- left the
     // encoded gradient in; its reverse through the encoding applies the loss seed itself
-    if (d_input && out.d_x) k_input_grad(b, out.d_x, seed_loss ? p.loss_total : nullptr, d_input, s);
+    if (d_input && out.d_x) k_input_grad(b, out.d_x, scale, d_input, s);
     mark(5);
 }
 
-// lnerf_render_maps_vjp: fused_train_step's sequence on the VJP instantiations of k1, seeded from the
+void fused_train_step(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b, float seed,
+                      int flags, const lnerf_outputs& out, hipStream_t s, hipEvent_t* ev, const FusedPlan* px,
+                      float* d_input) {
+    const bool seed_loss = (flags & LNERF_SEED_LOSS) != 0;
+    train_sequence(p, ws, bs, b, out,
+                   [&](const FusedPlan& q) { k16_launch(q, b, seed_loss ? 1.0f : seed, out, true, s); }, out.loss,
+                   seed_loss ? p.loss_total : nullptr, (flags & LNERF_ACCUMULATE) != 0, s, ev, px, d_input);
+}
+
+// lnerf_render_maps_vjp: the training sequence on the VJP instantiations of k1, seeded from the
 // caller's adjoints (seed 1, no loss: k1 leaves loss_part 0, and k1_reduce's launch is kept for the dW
 // product shifts it also forms).
 void fused_render_vjp(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b, int flags,
                       const lnerf_outputs& out, const comp::VjpArgs& vjp, hipStream_t s, hipEvent_t* ev,
                       const FusedPlan* px, float* d_input) {
-    auto mark = [&](int i) {
-        if (ev) (void)hipEventRecord(ev[i], s);
-    };
-    const size_t nred = (size_t)p.L * p.w_k * p.w_n + (size_t)p.L * p.w_n;
-    const unsigned rgrid = (unsigned)((nred + 255) / 256);
-    mark(0);
-    k16_pack(p, ws, bs, s);
-    mark(1);
-    k16_launch_vjp(p, b, out, vjp, s);
-    mark(2);
-    k1_reduce_launch(p, nullptr, s);
-    mark(3);
-    dw16_launch(p, s);
-    mark(4);
-    if (px && p.guard) {
-        // the floor guard's re-run on the bf16x6 split, gated on the device as in fused_train_step
-        k16_launch_vjp(*px, b, out, vjp, s);
-        k1_reduce_launch(*px, nullptr, s);
-        dw16_launch(*px, s);
-    }
-    const ReduceArgs ra = reduce_args(p, out, flags & LNERF_ACCUMULATE);
-    grad_reduce_kernel<<<rgrid, 256, 0, s>>>(ra);
-    if (d_input && out.d_x) k_input_grad(b, out.d_x, nullptr, d_input, s);
-    mark(5);
+    train_sequence(p, ws, bs, b, out, [&](const FusedPlan& q) { k16_launch_vjp(q, b, out, vjp, s); }, nullptr,
+                   nullptr, (flags & LNERF_ACCUMULATE) != 0, s, ev, px, d_input);
 }
 
 // Plain bf16 (config 5's inference precision) runs kr (lnerf_render.hip: every weight fragment
@@ -458,27 +340,29 @@ void fused_render_vjp(const FusedPlan& p, const float* ws, const float* bs, cons
 // precisions run k16's forward. Both read k16_pack's planes.
 bool fused_render_uses_kr(const FusedPlan& p, int flags) { return !(flags & LNERF_RENDER_K16) && kr_supported(p); }
 
-void fused_render(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b,
-                  const lnerf_outputs& out, hipStream_t s, int flags, hipEvent_t* ev) {
-    auto mark = [&](int i) {
-        if (ev) (void)hipEventRecord(ev[i], s);
-    };
+// The render sequence: pack, the forward kernel (kr() or k16(), fused_render_uses_kr), and with
+// reduce_loss the deterministic sum of its per-workgroup partial losses.
+template <class Kr, class K16>
+static void render_sequence(const FusedPlan& p, const float* ws, const float* bs, const lnerf_outputs& out,
+                            const Kr& kr, const K16& k16, bool reduce_loss, hipStream_t s, int flags,
+                            hipEvent_t* ev) {
+    const Marks mark{ev, s};
     mark(0);
     k16_pack(p, ws, bs, s);
     mark(1);
     int parts = p.num_wg;
     if (fused_render_uses_kr(p, flags)) {
-        kr_launch(p, b, out, s);
+        kr();
         parts = kr_num_wg(p);
     } else {
-        k16_launch(p, b, 1.0f, out, false, s);
+        k16();
     }
     mark(2);
-    if (parts > 4 * 256) {
+    if (reduce_loss && parts > 4 * 256) {
         const int per = (parts + kLossStage1 - 1) / kLossStage1;
         loss_stage1_kernel<<<kLossStage1, 256, 0, s>>>(p.loss_part, parts, per, p.loss_stage);
         loss_reduce_kernel<<<1, 256, 0, s>>>(p.loss_stage, kLossStage1, p.loss_total, out.loss);
-    } else {
+    } else if (reduce_loss) {
         loss_reduce_kernel<<<1, 256, 0, s>>>(p.loss_part, parts, p.loss_total, out.loss);
     }
     mark(3);
@@ -486,36 +370,18 @@ void fused_render(const FusedPlan& p, const float* ws, const float* bs, const ln
     mark(5);
 }
 
+void fused_render(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b,
+                  const lnerf_outputs& out, hipStream_t s, int flags, hipEvent_t* ev) {
+    render_sequence(p, ws, bs, out, [&] { kr_launch(p, b, out, s); }, [&] { k16_launch(p, b, 1.0f, out, false, s); },
+                    true, s, flags, ev);
+}
+
+// no target, no loss
 void fused_render_maps(const FusedPlan& p, const float* ws, const float* bs, const lnerf_batch& b,
                        const lnerf_outputs& out, const comp::MapsArgs& maps, hipStream_t s, int flags,
                        hipEvent_t* ev) {
-    auto mark = [&](int i) {
-        if (ev) (void)hipEventRecord(ev[i], s);
-    };
-    mark(0);
-    k16_pack(p, ws, bs, s);
-    mark(1);
-    int parts = p.num_wg;
-    if (fused_render_uses_kr(p, flags)) {
-        kr_launch_maps(p, b, out, maps, s);
-        parts = kr_num_wg(p);
-    } else {
-        k16_launch_maps(p, b, out, maps, s);
-    }
-    mark(2);
-    // the loss as fused_render sums it; no target, no loss
-    if (b.target) {
-        if (parts > 4 * 256) {
-            const int per = (parts + kLossStage1 - 1) / kLossStage1;
-            loss_stage1_kernel<<<kLossStage1, 256, 0, s>>>(p.loss_part, parts, per, p.loss_stage);
-            loss_reduce_kernel<<<1, 256, 0, s>>>(p.loss_stage, kLossStage1, p.loss_total, out.loss);
-        } else {
-            loss_reduce_kernel<<<1, 256, 0, s>>>(p.loss_part, parts, p.loss_total, out.loss);
-        }
-    }
-    mark(3);
-    mark(4);
-    mark(5);
+    render_sequence(p, ws, bs, out, [&] { kr_launch_maps(p, b, out, maps, s); },
+                    [&] { k16_launch_maps(p, b, out, maps, s); }, b.target != nullptr, s, flags, ev);
 }
 
 }  // namespace lnerf

@@ -7,19 +7,10 @@
 
 #include "lnerf.h"
 #include "lnerf_marshal.h"
+#include "lnerf_plan.h"
 
 namespace lnerf {
 
-constexpr int kWmaxParts = 32;   // blocks per layer of the max|W| pass before the fp16x3 packing
-constexpr int kHeadCols = 16;    // head columns with their own fp16x3 weight shift (k16 head outputs)
-constexpr int kDefaultDwGrid = 512;   // dW workgroups per step unless LNERF_OPT_DW_GRID says otherwise
-// The default budget for a batch of `samples` sample rows: 512 at the bench size and above, down to
-// 256 for smaller batches, where k2 is latency-bound and its time flat from 256 to 512 workgroups
-// while the in-order reduce over the splits grows with them (config 2, 32 768 samples, round 5:
-// 256 -> 0.073 ms per step, 512 -> 0.082; cfg3 keeps 512: 384 -> 0.88 ms of k2, 512 -> 0.73)
-__host__ __device__ constexpr int default_dw_grid(long long samples) {
-    return samples / 128 >= kDefaultDwGrid ? kDefaultDwGrid : samples / 128 <= 256 ? 256 : (int)(samples / 128);
-}
 // ---- exceptional rows of the fp16x3 dW split (round 6) ------------------------------------------
 // k2 (lnerf_dw16.hip) multiplies a sample's A row and G row as fp16 hi + lo pieces at per-row
 // exponent shifts balanced around the layer's product shift E_l (the smallest xa + xg over the
@@ -76,22 +67,11 @@ __device__ __forceinline__ void split_h2(float x0, float x1, float sc, unsigned&
     lo = __builtin_bit_cast(unsigned, (h2){l0, l1});
 }
 
-// ---- int24 activation slabs (fp16x3 training) --------------------------------------------------
-// k1 stores each A_l value (X for l = 0) that k2 reads as q = rint(x 2^(xa + 8)), xa = the
-// sample's row shift (fp16x3_shift of its max|x|, so |q| < 2^22), as the low 24 bits of the float
-// 1.5 2^23 + q (whose mantissa field is 2^22 + q); 4 values in 12 B. 2^-22 of the row's max|x|,
-// the precision fp16x3 keeps of it anyway; 25 % fewer bytes through HBM for the A half of the
-// slabs. G_l slabs stay fp32 (their rows span more range: tests/test_gpu_edge.py). A tile-block
-// (32 samples x 32 features) is then 3 KiB = 768 float slots instead of 1024.
-#ifndef LNERF_A24
-#define LNERF_A24 1
-#endif
-__host__ __device__ constexpr bool a24_slabs(int PL) { return PL == 2 && LNERF_A24 != 0; }
+// ---- int24 activation slabs (lnerf_plan.h: a24_slabs, a_tile_floats) ---------------------------
 // k1's shift byte of an activation row holding a NaN or an infinity (its max is non-finite): the row
 // is encoded at shift 0, and dw16 decodes its out-of-range codes (|q| >= 2^22: +-inf leaves 2^22,
 // NaN 1.5 2^23) as NaN, so a non-finite activation still makes its dW terms non-finite
 constexpr int kSexpNonFinite = -127;
-__host__ __device__ constexpr int a_tile_floats(int PL) { return a24_slabs(PL) ? 768 : 1024; }
 
 // ---- build fingerprint (lnerf_build_knobs): one bit per compile-time knob of the kernel objects
 // set away from the product default. The shipped library reports 0; tests and bench.py record it.
