@@ -194,6 +194,8 @@ enum {
                                  lnerf_ctx_timings counts it in [4] and [5]. At most 39
                                  frequencies. An extension (no loma counterpart: the reference
                                  encodes in numpy and never differentiates it).                */
+    LNERF_HASHGRID_REPRODUCIBLE = 65536, /* lnerf_hashgrid_grad only: d_table as float64 sums in a
+                                 fixed order, the same bits on every call (see there)           */
     LNERF_ONE_WAVE = 1024     /* removed in round 4 (the one-wave-per-SIMD kernel pair): an error.
                                  At most one LNERF_MFMA_* precision flag may be set; any fused-
                                  path flag (LNERF_MFMA_*, LNERF_K16_W4) on a shape the fused path
@@ -390,18 +392,47 @@ int lnerf_hashgrid_encode(const lnerf_hashgrid* grid, const float* table, const 
                           long long R, float* encoded, void* stream);
 
 /* The reverse of lnerf_hashgrid_encode from d_encoded (R, levels * F). `scale` (nullable) is a
- * device scalar multiplied in; `flags` is 0 or LNERF_ACCUMULATE. Either output may be NULL, both
- * NULL is an error; `table` may be NULL when d_points is.
+ * device scalar multiplied in; `flags` is 0, LNERF_ACCUMULATE, LNERF_HASHGRID_REPRODUCIBLE or both.
+ * Either output may be NULL, both NULL is an error; `table` may be NULL when d_points is.
  *   d_table (offset[levels], F): d_table[offset_l + entry_k][f] += (float)(scale weight_k
  * d_encoded[r][l F + f]) over every row, level and corner; cells that collide in a hashed level sum.
  * Without LNERF_ACCUMULATE the call first zeroes all offset[levels] * F values on the stream (entries
  * no sample touches are +0); with it the call adds into what is there and untouched entries keep
- * their bits. d_table is summed with float32 atomic adds (within a wave, adjacent rows that share an
- * entry are added together first; small dense levels are summed per workgroup in LDS): its last bits
- * depend on arrival order, so it is the ONE output of this library that is not bit-reproducible from
- * call to call, unlike d_points and encoded. An entry that receives n terms is within
+ * their bits. In the default mode d_table is summed with float32 atomic adds (within a wave, adjacent
+ * rows that share an entry are added together first; small dense levels are summed per workgroup in
+ * LDS): its last bits depend on arrival order, so the default mode of d_table is not bit-reproducible
+ * from call to call -- the one output of this library that is not, unlike d_points and encoded --
+ * and under LNERF_HASHGRID_REPRODUCIBLE (below) it is. In the default mode an entry that receives n
+ * terms is within
  *     2^-23 |exact| + (n + 2) 2^-24 sum |term|
  * of the exact sum (one float32 rounding per term and at most n float32 adds, in any order).
+ *   LNERF_HASHGRID_REPRODUCIBLE changes how d_table is formed and nothing else (d_points has the
+ * same bits with and without it; with d_table == NULL it is accepted and takes no scratch). For
+ * entry e of level l and feature f, a term is
+ *     t(r, k, f) = ((double)scale weight_k(r)) (double)d_encoded[r][l F + f]
+ * with the encoder's float64 weight (fx fy) fz: two float64 products in that order, no contraction,
+ * not rounded to float32. The terms of the contributions (r, k) whose corner maps to e, taken in
+ * ascending contribution id c = 8 r + k as t_0 .. t_{n-1}, are summed in float64 in this order:
+ *     partial_q = ((+0 + t_{8q}) + t_{8q+1}) + ... + t_{min(8q+7, n-1)}     q = 0 .. ceil(n / 8) - 1
+ *     sum       = ((+0 + partial_0) + partial_1) + ...
+ * i.e. runs of eight consecutive positions of the entry's ascending-c list, then the partial sums in
+ * ascending order (n <= 8: the plain sequential sum). The order depends on that list alone, never on
+ * launch geometry, the number of compute units, arrival order or timing. Then d_table[e][f] =
+ * (float)sum, or under LNERF_ACCUMULATE d_table[e][f] + (float)sum (one float32 add). An entry that
+ * receives no term is +0 without LNERF_ACCUMULATE; with it the entry is skipped and keeps its bits
+ * (a held -0 stays -0). A NaN or infinity in a row's d_encoded reaches exactly that row's entries,
+ * as in the default mode. The same inputs give the same bits on every call, stream and device of
+ * this kind; the result is within
+ *     2^-24 |exact| + 2^-149 + (n + 1) 2^-52 sum |term|
+ * of the exact sum (one float32 rounding; n float64 products and adds). No float atomics: per level
+ * a stable radix sort brings each entry's ids together (keys: the entry indices, ceil(log2 E_l)
+ * bits) and a segmented float64 sum writes one row per touched entry. R <= 2^28 under the flag (a
+ * contribution id must fit 32 bits; more is an error and nothing is launched or written) and d_table
+ * must be aligned like `table`, to min(16, 4 F) bytes (rows are stored whole). Scratch comes from
+ * the stream's memory pool for the duration of the call (hipMallocAsync / hipFreeAsync on `stream`):
+ * 192 bytes per row -- per contribution two 4-byte keys, two 4-byte ids and one float64 factor,
+ * one level at a time, so independent of `levels` -- plus the sort's own temporary storage;
+ * lnerf_hashgrid_grad_scratch returns the exact count.
  *   d_points (R, 3): d_points[r][c] = (float)(scale sum_l ((sum_f d_encoded[r][l F + f]
  * (sum_k (d weight_k / d pos_c) table_k[f])) (res_l - 1) / (hi_c - lo_c))), d weight_k / d pos_x =
  * +- fy fz (+ where bit x of k is set), likewise y and z; float64 in that fixed order, rounded once:
@@ -410,6 +441,11 @@ int lnerf_hashgrid_encode(const lnerf_hashgrid* grid, const float* table, const 
 int lnerf_hashgrid_grad(const lnerf_hashgrid* grid, const float* table, const float* points,
                         long long R, const float* d_encoded, const float* scale, int flags,
                         float* d_table, float* d_points, void* stream);
+
+/* The bytes an lnerf_hashgrid_grad call with LNERF_HASHGRID_REPRODUCIBLE, a d_table and R rows takes
+ * from the stream's memory pool while it runs (0 for R == 0), or a negative code. Needs a device
+ * (the sort sizes its temporary storage for it); launches and writes nothing. R <= 2^28. */
+long long lnerf_hashgrid_grad_scratch(const lnerf_hashgrid* grid, long long R, void* stream);
 
 /* ---- Occupancy grid ---------------------------------------------------------------------------
  * Where the scene is empty, known without a network evaluation: a coarse grid of res^3 cells over

@@ -1043,16 +1043,35 @@ extern "C" int lnerf_hashgrid_grad(const lnerf_hashgrid* grid, const float* tabl
     return guard_int([&]() {
         const char* what = "lnerf_hashgrid_grad";
         const HgParams g = hashgrid_params(what, grid);
-        if (flags & ~LNERF_ACCUMULATE) fail("%s: flags 0x%x: only LNERF_ACCUMULATE applies", what, flags);
+        if (flags & ~(LNERF_ACCUMULATE | LNERF_HASHGRID_REPRODUCIBLE))
+            fail("%s: flags 0x%x: only LNERF_ACCUMULATE and LNERF_HASHGRID_REPRODUCIBLE apply", what, flags);
+        const bool ordered = (flags & LNERF_HASHGRID_REPRODUCIBLE) != 0;
         if (!d_table && !d_points) fail("%s: d_table and d_points are both NULL", what);
         if (!points || !d_encoded) fail("%s: null argument", what);
         if (d_points && !table) fail("%s: d_points needs the table", what);
         if (d_points) hashgrid_check_aligned(what, "table", table, g.features);
         hashgrid_check_rows(what, R);
+        // a contribution id 8 r + k must fit 32 bits
+        if (ordered && R > (1ll << 28)) fail("%s: more than 2^28 rows under LNERF_HASHGRID_REPRODUCIBLE", what);
+        if (ordered && d_table) hashgrid_check_aligned(what, "d_table", d_table, g.features);   // rows are stored whole
         if (R == 0) return;
         need_device();
         hipStream_t s = (hipStream_t)stream;
-        if (d_table) {
+        if (d_table && ordered) {
+            // stream-ordered scratch, as lnerf_pose_grad: calls on several streams never share it
+            size_t bytes = 0;
+            HIP_OK(k_hashgrid_sorted_scratch_bytes(g, R, s, &bytes));
+            void* scratch = nullptr;
+            HIP_OK(hipMallocAsync(&scratch, bytes, s));
+            hipError_t done = hipSuccess;
+            if (!(flags & LNERF_ACCUMULATE))
+                done = hipMemsetAsync(d_table, 0, (size_t)grid->offset[g.levels] * g.features * sizeof(float), s);
+            if (done == hipSuccess)
+                done = k_hashgrid_grad_table_sorted(g, points, R, d_encoded, scale, (flags & LNERF_ACCUMULATE) != 0,
+                                                    d_table, scratch, s);
+            HIP_OK(hipFreeAsync(scratch, s));
+            if (done != hipSuccess) fail("%s: the sorted d_table failed: %s", what, hipGetErrorString(done));
+        } else if (d_table) {
             if (!(flags & LNERF_ACCUMULATE))
                 HIP_OK(hipMemsetAsync(d_table, 0, (size_t)grid->offset[g.levels] * g.features * sizeof(float), s));
             k_hashgrid_grad_table(g, points, R, d_encoded, scale, d_table, s);
@@ -1063,6 +1082,22 @@ extern "C" int lnerf_hashgrid_grad(const lnerf_hashgrid* grid, const float* tabl
             check_launch(what);
         }
     });
+}
+
+extern "C" long long lnerf_hashgrid_grad_scratch(const lnerf_hashgrid* grid, long long R, void* stream) {
+    long long total = 0;
+    const int rc = guard_int([&]() {
+        const char* what = "lnerf_hashgrid_grad_scratch";
+        const HgParams g = hashgrid_params(what, grid);
+        hashgrid_check_rows(what, R);
+        if (R > (1ll << 28)) fail("%s: more than 2^28 rows under LNERF_HASHGRID_REPRODUCIBLE", what);
+        if (R == 0) return;
+        need_device();
+        size_t bytes = 0;
+        HIP_OK(k_hashgrid_sorted_scratch_bytes(g, R, (hipStream_t)stream, &bytes));
+        total = (long long)bytes;
+    });
+    return rc ? rc : total;
 }
 
 // ---- occupancy grid (lnerf_occgrid.hip): free functions on a stream, no context -------------------

@@ -38,5 +38,14 @@ void k_hashgrid_grad_table(HgParams g, const float* points, long long R, const f
 void k_hashgrid_grad_points(const HgParams& g, const float* table, const float* points, long long R,
                             const float* d_encoded, const float* scale, float* d_points, hipStream_t s);
 
+// lnerf_hashgrid_sorted.hip: d_table under LNERF_HASHGRID_REPRODUCIBLE. R <= 2^28; d_table aligned
+// like the table and, without `accumulate`, zeroed by the caller. `scratch` holds the bytes
+// k_hashgrid_sorted_scratch_bytes gives for the same g and R; the work is enqueued on s, level by
+// level. Either returns the first HIP error it meets (what was enqueued before it still runs).
+hipError_t k_hashgrid_sorted_scratch_bytes(const HgParams& g, long long R, hipStream_t s, size_t* bytes);
+hipError_t k_hashgrid_grad_table_sorted(const HgParams& g, const float* points, long long R, const float* d_encoded,
+                                        const float* scale, bool accumulate, float* d_table, void* scratch,
+                                        hipStream_t s);
+
 }  // namespace lnerf
 #endif

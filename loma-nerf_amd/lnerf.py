@@ -38,6 +38,7 @@ K16_W4 = 4096      # fused path: k16 on 4-wave 64-sample workgroups, two per CU 
 HEAD_FIT = 8192    # the mlp_fit head (sigmoid on every output, no compositing; samples = 1)
 RENDER_K16 = 16384  # render (plain bf16) on k16's forward instead of kr (A/B)
 WANT_DINPUT = 32768  # d_x = the gradient with respect to the batch's own x, in x's layout
+HASHGRID_REPRODUCIBLE = 65536  # lnerf_hashgrid_grad: d_table as ordered float64 sums, the same bits every call
 
 OPT_DW_GRID = 1    # lnerf_ctx_set_option: dW workgroups per step (0 = default 512)
 
@@ -51,7 +52,7 @@ EXPORTED_SYMBOLS = [
     "lnerf_ctx_guard_fired", "lnerf_input_grad", "lnerf_pose_grad", "lnerf_ctx_workspace_used",
     "lnerf_render_maps", "lnerf_sample_stratified", "lnerf_sample_importance", "lnerf_ray_points",
     "lnerf_ray_points_grad", "lnerf_render_maps_vjp", "lnerf_hashgrid_init", "lnerf_hashgrid_encode",
-    "lnerf_hashgrid_grad", "lnerf_occgrid_cell_points", "lnerf_occgrid_update", "lnerf_occgrid_threshold",
+    "lnerf_hashgrid_grad", "lnerf_hashgrid_grad_scratch", "lnerf_occgrid_cell_points", "lnerf_occgrid_update", "lnerf_occgrid_threshold",
     "lnerf_sample_occupancy",
 ]
 
@@ -246,6 +247,9 @@ def configure(lib: ctypes.CDLL) -> None:
         lib.lnerf_hashgrid_encode.restype = ci
         lib.lnerf_hashgrid_grad.argtypes = [hg, vp, vp, ll, vp, vp, ci, vp, vp, vp]
         lib.lnerf_hashgrid_grad.restype = ci
+        if hasattr(lib, "lnerf_hashgrid_grad_scratch"):
+            lib.lnerf_hashgrid_grad_scratch.argtypes = [hg, ll, vp]
+            lib.lnerf_hashgrid_grad_scratch.restype = ll
     if hasattr(lib, "lnerf_sample_occupancy"):   # (older in-tree A/B builds lack the occupancy grid)
         vp, ci, cf, ll = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_longlong
         og = ctypes.POINTER(LnerfOccGrid)
@@ -779,13 +783,17 @@ class Engine:
         return out
 
     def hashgrid_grad(self, grid: HashGrid, table, points, d_encoded, scale=None, accumulate: bool = False,
-                      d_table=None, want_d_points: bool = False, want_d_table: bool = True):
+                      d_table=None, want_d_points: bool = False, want_d_table: bool = True,
+                      reproducible: bool = False):
         """lnerf_hashgrid_grad, the reverse of hashgrid_encode: (d_table (total_entries, F), d_points
         (R, 3)) from d_encoded (R, grid.width) -- StepResult.d_x of an INPUT_ENCODED step with want_dx.
         `d_table` may be a buffer to write (accumulate=True: to add into; it is then required); an
         output that is not asked for is None. `table` may be None unless want_d_points. `scale` is an
-        optional float32 device scalar multiplied in. d_table is summed with float32 atomics (its last
-        bits vary from call to call); d_points is bit-reproducible."""
+        optional float32 device scalar multiplied in. By default d_table is summed with float32 atomics
+        (its last bits vary from call to call); with reproducible=True (HASHGRID_REPRODUCIBLE) it is a
+        float64 sum per entry in a fixed order, rounded once: the same bits on every call, from scratch
+        the call takes from the stream's memory pool (hashgrid_grad_scratch bytes). d_points is
+        bit-reproducible either way and has the same bits in both modes."""
         torch = self.torch
         if points.dim() != 2:
             raise ValueError(f"points is {tuple(points.shape)}, expected (R, 3)")
@@ -808,12 +816,20 @@ class Engine:
         else:
             d_table = None
         d_points = torch.empty(R, 3, dtype=torch.float32, device=points.device) if want_d_points else None
+        flags = (ACCUMULATE if accumulate else 0) | (HASHGRID_REPRODUCIBLE if reproducible else 0)
         rc = self.lib.lnerf_hashgrid_grad(ctypes.byref(grid.struct), _ptr(table), _ptr(points), R, _ptr(d_encoded),
-                                          _ptr(scale), ACCUMULATE if accumulate else 0, _ptr(d_table),
-                                          _ptr(d_points), self._stream())
+                                          _ptr(scale), flags, _ptr(d_table), _ptr(d_points), self._stream())
         if rc != 0:
             raise RuntimeError(f"lnerf_hashgrid_grad: {last_error()}")
         return d_table, d_points
+
+    def hashgrid_grad_scratch(self, grid: HashGrid, rows: int) -> int:
+        """lnerf_hashgrid_grad_scratch: the bytes a hashgrid_grad(..., reproducible=True) call on `rows`
+        rows takes from the stream's memory pool while it runs."""
+        n = self.lib.lnerf_hashgrid_grad_scratch(ctypes.byref(grid.struct), int(rows), self._stream())
+        if n < 0:
+            raise RuntimeError(f"lnerf_hashgrid_grad_scratch: {last_error()}")
+        return int(n)
 
     def _dev(self, name, t, dtype, shape=None):
         """`t` must be a contiguous tensor of `dtype` on this engine's device (of `shape`, if given)."""
@@ -1096,8 +1112,8 @@ def _hashgrid_fn():
 
     class HashGridFn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, engine, grid, table, points):
-            ctx.engine, ctx.grid = engine, grid
+        def forward(ctx, engine, grid, table, points, reproducible):
+            ctx.engine, ctx.grid, ctx.reproducible = engine, grid, bool(reproducible)
             ctx.save_for_backward(table, points)
             return engine.hashgrid_encode(grid, table, points)
 
@@ -1106,19 +1122,21 @@ def _hashgrid_fn():
             table, points = ctx.saved_tensors
             need_t, need_p = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
             if not (need_t or need_p):
-                return None, None, None, None
+                return None, None, None, None, None
             d_table, d_points = ctx.engine.hashgrid_grad(ctx.grid, table, points, g.contiguous().float(),
-                                                         want_d_table=need_t, want_d_points=need_p)
-            return None, None, d_table, d_points
+                                                         want_d_table=need_t, want_d_points=need_p,
+                                                         reproducible=ctx.reproducible)
+            return None, None, d_table, d_points, None
 
     _HASHGRID_FN = HashGridFn
     return HashGridFn
 
 
-def hashgrid_autograd(engine: Engine, grid: HashGrid, table, points):
+def hashgrid_autograd(engine: Engine, grid: HashGrid, table, points, reproducible: bool = False):
     """The hash-grid encoding as a differentiable torch tensor: a torch.autograd.Function whose forward
     is Engine.hashgrid_encode and whose backward is ONE Engine.hashgrid_grad call. Gradients reach
-    `table` and, if it requires grad, `points`. Feed the result to a torch MLP, or to
+    `table` and, if it requires grad, `points`; reproducible=True makes the table gradient the ordered
+    float64 sum of HASHGRID_REPRODUCIBLE (the same bits on every backward). Feed the result to a torch MLP, or to
     render_maps_autograd(..., input_mode=INPUT_ENCODED) to train the grid under any loss on the maps:
 
         x = hashgrid_autograd(eng, grid, table, points)
@@ -1126,4 +1144,4 @@ def hashgrid_autograd(engine: Engine, grid: HashGrid, table, points):
                                       want=("color",))
         ((color - target) ** 2).sum().backward()      # table.grad, ws.grad, bs.grad
     """
-    return _hashgrid_fn().apply(engine, grid, table, points)
+    return _hashgrid_fn().apply(engine, grid, table, points, reproducible)

@@ -151,14 +151,16 @@ def render_hierarchical_image(engine, coarse, fine, width, K, c2w, samples, n_fi
 
 
 def hashgrid_step(engine, grid, table, mlp, ws, bs, rays, sample_t, target, *, seed=None, flags=0,
-                  grads=None, d_table=None, accumulate=False, want_d_rays=True):
+                  grads=None, d_table=None, accumulate=False, want_d_rays=True, reproducible=False):
     """One training step of a hash-grid NeRF on the device (an extension; the reference's only encoder
     is pos_encoding.py): Engine.ray_points turns rays (n, 6) and per-ray depths sample_t (n, S) into
     points and dists, Engine.hashgrid_encode encodes them with `table`, Engine.train_step runs the MLP,
     the compositing and the loss on the encoded rows (INPUT_ENCODED, WANT_DX) and
     Engine.hashgrid_grad reverses the encoding from its d_x. `seed` and `flags` as train_step (None
     seeds with the batch loss); d_x carries the seed, so d_table and d_rays do too. `d_table` may be a
-    buffer to write, or with accumulate=True to add into. Returns a dict: loss, acc_color, d_ws, d_bs,
+    buffer to write, or with accumulate=True to add into. reproducible=True sums d_table in the fixed
+    float64 order of lnerf.HASHGRID_REPRODUCIBLE: every returned tensor then has the same bits on every
+    call with the same inputs. Returns a dict: loss, acc_color, d_ws, d_bs,
     grads (train_step's packed buffer), d_table (total_entries, F), d_points (n*S, 3) and d_rays (n, 6)
     = Engine.ray_points_grad of d_points, which feeds Engine.pose_grad (both None without
     want_d_rays)."""
@@ -169,7 +171,7 @@ def hashgrid_step(engine, grid, table, mlp, ws, bs, rays, sample_t, target, *, s
     r = engine.train_step(mlp, ws, bs, x, dists, target, samples=S, input_mode=lnerf.INPUT_ENCODED, seed=seed,
                           flags=flags, grads=grads, want_dx=True)
     d_table, d_points = engine.hashgrid_grad(grid, table, points, r.d_x, accumulate=accumulate, d_table=d_table,
-                                             want_d_points=want_d_rays)
+                                             want_d_points=want_d_rays, reproducible=reproducible)
     d_rays = engine.ray_points_grad(sample_t, d_points) if want_d_rays else None
     return dict(loss=r.loss, acc_color=r.acc_color, d_ws=r.d_ws, d_bs=r.d_bs, grads=r.grads, d_x=r.d_x,
                 d_table=d_table, d_points=d_points, d_rays=d_rays)
