@@ -20,7 +20,8 @@
 //  * MFMA operands come out of that sample-major image transposed by ds_read_b64_tr_b16: lane
 //    (feature l & 31, samples 8 (l >> 5) ..+7) takes two 4-sample x 16-feature blocks;
 //  * each wave owns a TI x TJ block of 32 x 32 output tiles (2 x 4 for the hidden layers);
-//  * db from the same registers (per-feature partial sums, reduced in LDS at the end);
+//  * db from the same registers (per-feature partial sums beside the G rounds' split, reduced in
+//    LDS at the end);
 //  * partials per split, summed in order by grad_reduce_kernel (deterministic, no atomics);
 //  * under fp16x3, the exceptional rows of the split's range (lnerf_internal.h kXrowD0: rows far
 //    below or above the layer's product scale, every ray's last sample) are dropped from the fp16x3
@@ -131,7 +132,6 @@ __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane
 // part is wave-uniform.
 struct RowMap {
     int lane;        // per-thread float offset inside a tile's half-block
-    int hstride;     // floats between the two half-blocks of a 32-sample block's tile
     int rowo;        // the thread's first feature inside its 32-feature tile (4 consecutive)
     int isamp;       // the thread's sample inside the half-block (its LDS image row)
     int tile[kRounds];   // wave-uniform: the 32-feature tile of round i (tile 0 for tiles past the layer)
@@ -142,7 +142,6 @@ __device__ __forceinline__ RowMap row_map(int kt, int nt) {
     RowMap m;
     const int t = threadIdx.x, u = t & 127;
     m.lane = 4 * u;
-    m.hstride = 512;
     m.rowo = 16 * ((t >> 6) & 1) + 4 * (t & 3);
     m.isamp = (t & 63) >> 2;
     const int w2 = wave_id() >> 1;
@@ -190,13 +189,25 @@ __device__ __forceinline__ void sample_shifts(unsigned e, int E, int& ea, int& e
 // idle image and add nothing to db (the callers' hb < hb1 guards).
 // `rounds`: bit i = round i is issued (the rotation issues a half-block's rounds one by one, hb_step3)
 constexpr int kAllRounds = (1 << kRounds) - 1;
+// bytes of one tile's half-block in the A slab (int24: 512 x 3 B) and in the G slab
 template <bool A24>
-__device__ __forceinline__ void issue_loads(const float* A, const float* G, int kt, int nt, const RowMap& m,
-                                            int hb, int hb_end, Loads& L, int rounds = kAllRounds) {
-    const bool in = hb < hb_end;
-    const int hbc = in ? hb : max(0, hb_end - 1);
+constexpr int a_half_bytes() { return A24 ? 1536 : 2048; }
+constexpr int kGHalfBytes = 2048;
+
+// The wave-uniform bases of half-block hbc: a 32-sample block holds the layer's tiles one after the
+// other, each as two half-blocks.
+template <bool A24>
+__device__ __forceinline__ void hb_bases(const float* A, const float* G, int kt, int nt, int hbc,
+                                         const unsigned char*& pa, const unsigned char*& pg) {
     const int blk = hbc >> 1, half = hbc & 1;
-    const float* pg = G + (size_t)blk * nt * 1024 + half * m.hstride;
+    pa = (const unsigned char*)A + ((size_t)blk * kt * (2 * a_half_bytes<A24>()) + half * a_half_bytes<A24>());
+    pg = (const unsigned char*)G + ((size_t)blk * nt * (2 * kGHalfBytes) + half * kGHalfBytes);
+}
+
+// The loads of the half-block whose A and G bases are pa and pg.
+template <bool A24>
+__device__ __forceinline__ void issue_loads_at(const unsigned char* pa, const unsigned char* pg, int kt, int nt,
+                                               const RowMap& m, Loads& L, int rounds) {
     if (!(rounds & ((1 << kRPO) - 1))) {
     } else if constexpr (A24) {
         // int24 A slab (k1 store_slab_step24): a tile-block is 3 KiB, its half-blocks 1.5 KiB
@@ -206,7 +217,6 @@ __device__ __forceinline__ void issue_loads(const float* A, const float* G, int 
         // offset into a 64-bit per-thread base and adds the uniform part with 64-bit vector adds,
         // two registers for the whole loop and three adds per load). The descriptor ends with
         // this half-block's last tile.
-        const unsigned char* pa = (const unsigned char*)A + ((size_t)blk * kt * 3072 + half * 1536);
         const __amdgpu_buffer_rsrc_t rs =
             __builtin_amdgcn_make_buffer_rsrc((void*)pa, 0, kt * 3072 - 1536, 0x00020000);
 #pragma unroll
@@ -218,14 +228,54 @@ __device__ __forceinline__ void issue_loads(const float* A, const float* G, int 
                 L.a24[i] = __builtin_bit_cast(fx3, __builtin_amdgcn_raw_buffer_load_b96(rs, 3 * m.lane, m.tile[i] * 3072, 2));
         }
     } else {
-        const float* pa = A + (size_t)blk * kt * 1024 + half * m.hstride;
+        const float* fa = (const float*)pa;
 #pragma unroll
         for (int i = 0; i < kRPO; ++i)
-            if (rounds >> i & 1) L.v[i] = __builtin_nontemporal_load((const fx4*)(pa + m.tile[i] * 1024 + m.lane));
+            if (rounds >> i & 1) L.v[i] = __builtin_nontemporal_load((const fx4*)(fa + m.tile[i] * 1024 + m.lane));
     }
+    // the G rounds the same way (as global loads every tile's base is a 64-bit scalar add of its own):
+    // the descriptor spans this half-block of the layer's nt tiles, and a tile past the layer reads tile 0
+    if (!(rounds >> kRPO)) return;
+    const __amdgpu_buffer_rsrc_t rg =
+        __builtin_amdgcn_make_buffer_rsrc((void*)pg, 0, nt * (2 * kGHalfBytes) - kGHalfBytes, 0x00020000);
+    typedef unsigned ux4 __attribute__((ext_vector_type(4)));
 #pragma unroll
     for (int i = kRPO; i < kRounds; ++i)
-        if (rounds >> i & 1) L.v[i] = __builtin_nontemporal_load((const fx4*)(pg + m.tile[i] * 1024 + m.lane));
+        if (rounds >> i & 1)
+            L.v[i] = __builtin_bit_cast(fx4, (ux4)__builtin_amdgcn_raw_buffer_load_b128(rg, 4 * m.lane, m.tile[i] * (2 * kGHalfBytes), 2));
+}
+
+// The wave-uniform state of the rotation (hb_step3, hb_step2), advanced from step to step by scalar
+// adds instead of being rebuilt from the half-block's index with 64-bit multiplies and the range
+// clamp. pa, pg: the bases of the newest half-block loaded. Inside a range the next half-block lies
+// a tile's half-block further (the block's second half) or the rest of the block further (the next
+// block's first half), in turn: da, dg hold the next step and are flipped by d = block - d. Once the
+// next half-block lies past the range's end the bases stay (the loads repeat the last half-block)
+// until the chunk ends.
+struct Rot {
+    const unsigned char *pa, *pg;
+    unsigned da, dg, ba, bg;
+    unsigned img;
+};
+// at half-block hb0, the first of a chunk
+template <bool A24>
+__device__ __forceinline__ Rot rot_begin(const float* A, const float* G, int kt, int nt, int hb0) {
+    Rot r;
+    hb_bases<A24>(A, G, kt, nt, hb0, r.pa, r.pg);
+    r.ba = kt * (2 * a_half_bytes<A24>());
+    r.bg = nt * (2 * kGHalfBytes);
+    r.da = hb0 & 1 ? r.ba - a_half_bytes<A24>() : a_half_bytes<A24>();
+    r.dg = hb0 & 1 ? r.bg - kGHalfBytes : kGHalfBytes;
+    r.img = 0;
+    return r;
+}
+// to half-block hb's loads (the one after the newest), at most the range's last
+__device__ __forceinline__ void rot_advance(Rot& r, int hb, int hb1) {
+    const bool in = hb < hb1;
+    r.pa += in ? r.da : 0u;
+    r.pg += in ? r.dg : 0u;
+    r.da = r.ba - r.da;
+    r.dg = r.bg - r.dg;
 }
 
 // The 4 values of an int24 A round (k1 store_slab_step24): 3 dwords holding the low 24 bits of
@@ -238,13 +288,19 @@ __device__ __forceinline__ fx4 decode_a24(const fx3& raw) {
     typedef unsigned ux3 __attribute__((ext_vector_type(3)));
     const ux3 d = __builtin_bit_cast(ux3, raw);
     const unsigned d0 = d[0], d1 = d[1], d2 = d[2];
-    const unsigned m0 = d0 & 0xFFFFFFu;
-    const unsigned m1 = __builtin_amdgcn_alignbit(d1, d0, 24) & 0xFFFFFFu;
-    const unsigned m2 = __builtin_amdgcn_alignbit(d2, d1, 16) & 0xFFFFFFu;
-    const unsigned m3 = d2 >> 8;
+    // value 3 is one v_alignbit_b32 whose high operand is the exponent byte 0x4B (no OR of its own);
+    // values 1 and 2 are a v_perm_b32 (extract, top byte cleared) and an OR, value 0 an AND and an
+    // OR. One v_and_or_b32 for value 0 needs 0x4B000000 in a vector register for the whole kernel
+    // (the instruction takes no literal and one scalar operand on gfx950, and a known constant is
+    // rematerialised by a v_mov_b32 in front of every use): built, 6 VALU fewer per iteration of
+    // the hidden layers' loop for one register and 12 more spilled dwords, no faster; not kept.
+    const unsigned y0 = (d0 & 0xFFFFFFu) | 0x4B000000u;
+    const unsigned y1 = (__builtin_amdgcn_alignbit(d1, d0, 24) & 0xFFFFFFu) | 0x4B000000u;
+    const unsigned y2 = (__builtin_amdgcn_alignbit(d2, d1, 16) & 0xFFFFFFu) | 0x4B000000u;
+    const unsigned y3 = __builtin_amdgcn_alignbit(0x4Bu, d2, 8);
     constexpr float kMagic = 12582912.0f;   // 1.5 2^23
-    return fx4{__builtin_bit_cast(float, 0x4B000000u | m0) - kMagic, __builtin_bit_cast(float, 0x4B000000u | m1) - kMagic,
-               __builtin_bit_cast(float, 0x4B000000u | m2) - kMagic, __builtin_bit_cast(float, 0x4B000000u | m3) - kMagic};
+    return fx4{__builtin_bit_cast(float, y0) - kMagic, __builtin_bit_cast(float, y1) - kMagic,
+               __builtin_bit_cast(float, y2) - kMagic, __builtin_bit_cast(float, y3) - kMagic};
 }
 
 // x = hi + mid + lo, round-to-nearest bf16 of each remainder (every remainder is exact in f32).
@@ -370,7 +426,7 @@ __device__ __forceinline__ SampleScale decode_scale(const float2& t) {
 // half-blocks past a chunk's end with entries: the rotation splits up to two and fetches a step ahead
 constexpr int kTabPast = 4;
 // Entries of the half-blocks [c0, c1 + kTabPast) of layer words `se`. A half-block past c1 takes the
-// words of half-block c1 - 1, whose values its loads fetch (issue_loads), at scale 0. Returns
+// words of half-block c1 - 1, whose values its loads fetch (rot_advance), at scale 0. Returns
 // whether this thread met an exceptional row inside the range (fp16x3: xrow_pass).
 template <int PL>
 __device__ __forceinline__ bool fill_scales(float2* tab, const unsigned* se, int E, int c0, int c1) {
@@ -498,13 +554,28 @@ __device__ __forceinline__ void mma_col(const bf8 (&ap)[TI][nplanes(PL)], const 
     }
 }
 
+// db: a thread's G values of a half-block are 4 features of one sample per G round, summed per
+// feature over the split's range (dw_split reduces the 16 samples of a feature through LDS). Plain
+// floats added one by one: an fx4 `+=` is legalised to v_pk_add_f32, which costs more than two
+// v_add_f32 beside MFMAs. `on`: the half-block lies inside the range (wave-uniform; the steps
+// past the range's end hold the last half-block's values again). A branch, not a select per sum:
+// the volatile statement keeps the compiler from speculating the block (round_values).
+typedef float DbSums[kRPO][4];
+__device__ __forceinline__ void db_add(DbSums& dbs, const Loads& L, int r, bool on) {
+    if (on) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dbs[r][j] += L.v[kRPO + r][j];
+        asm volatile("" : "+v"(dbs[r][0]));
+    }
+}
+
 // The wave's TI x TJ tile block (TI 32-row tiles of A, TJ of G) on one half-block image, with
 // the split of the next half-block interleaved (round k beside output column tile k), so the
 // VALU split issues under the MFMAs. Branch-free (ACTIVE is a template parameter; past the
 // split's last half-block the zeroed loads land in the idle image buffer).
 //
 // Fragment read-ahead (fp16x3, LNERF_DW16_AHEAD): the first things a wave issues after the barrier
-// are this half-block's A fragments and column 0's G planes; `pre` (the db sums, the scale fetch)
+// are this half-block's A fragments and column 0's G planes; `pre` (the scale fetch)
 // follows them. Column j + 1's planes are read while column j's MFMAs issue, each in place: its lo
 // plane into the lo buffer as soon as column j's a_hi g_lo products are out (the only ones that
 // use it), its hi plane into the hi buffer once the other products of column j are out; the next
@@ -520,8 +591,8 @@ __device__ __forceinline__ void mma_col(const bf8 (&ap)[TI][nplanes(PL)], const 
 #endif
 template <int PL, int TI, int TJ, bool ACTIVE, bool FULL, typename Pre, typename Mid>
 __device__ __forceinline__ void block_mma(const unsigned char* img, int a0, int g0, fx16 (&acc)[TI][TJ],
-                                          const Loads& nl, unsigned char* nxt, const RowMap& m, Pre&& pre,
-                                          Mid&& mid) {
+                                          const Loads& nl, unsigned char* nxt, const RowMap& m, DbSums& dbs,
+                                          bool dbon, Pre&& pre, Mid&& mid) {
     const unsigned char* fl = img;
     constexpr int NP = nplanes(PL);
     constexpr bool AHEAD = LNERF_DW16_AHEAD != 0 && LNERF_DW16_PMAJOR != 0 && PL == 2;
@@ -559,6 +630,8 @@ __device__ __forceinline__ void block_mma(const unsigned char* img, int a0, int 
             const int i = k * RPS + r;
             if (i < kRounds && (FULL || m.ok[i]))
                 write_planes_row<PL>(round_values<PL>(nl, i, sc.marked, anym), i, nxt, sa, sg, m);
+            // db of the half-block being split, beside the split of the same registers
+            if (i >= kRPO && i < kRounds) db_add(dbs, nl, i - kRPO, dbon);
         }
     };
 #pragma unroll
@@ -611,41 +684,39 @@ __device__ __forceinline__ void block_mma(const unsigned char* img, int a0, int 
 template <int PL, int TI, int TJ, bool ACTIVE, bool FULL, int I>
 __device__ __forceinline__ void hb_step3(const float* A, const float* G, const float2* tab, int kt, int nt,
                                          const RowMap& m, int hb, int hb0, int hb1, int a0, int g0,
-                                         fx16 (&acc)[TI][TJ], Loads& L0, Loads& L1, Loads& L2, fx4 (&dbs)[kRPO],
-                                         unsigned char* lds, float2& scn) {
+                                         fx16 (&acc)[TI][TJ], Loads& L0, Loads& L1, Loads& L2, DbSums& dbs,
+                                         unsigned char* lds, float2& scn, Rot& rot) {
     constexpr int kIB = image_bytes<PL>();
     Loads& fr = I == 0 ? L0 : I == 1 ? L1 : L2;
     const Loads& nx = I == 0 ? L1 : I == 1 ? L2 : L0;
-    // the db sums and the scales of hb + 1 (`tab`: this thread's sample's
-    // column of the scale table, entry 0 = half-block hb0)
+    // the scales of hb + 1 (`tab`: this thread's sample's column of the scale table, entry 0 =
+    // half-block hb0)
     auto pre = [&]() {
-        if (hb + 1 < hb1) {
-#pragma unroll
-            for (int i = 0; i < kRPO; ++i) dbs[i] += nx.v[kRPO + i];
-        }
         // (hb + 1's entry was fetched a step ahead, so nothing here waits for the table; hb + 2's follows)
         const SampleScale sc = decode_scale(scn);
         scn = tab[(hb + 2 - hb0) * 16];
         return sc;
     };
     // (round_by_round above)
-    auto mid = [&](int rounds) { issue_loads<a24k(PL)>(A, G, kt, nt, m, hb + LNERF_DW16_DEPTH, hb1, fr, rounds); };
-    const int cur = (hb - hb0) & 1;
-    block_mma<PL, TI, TJ, ACTIVE, FULL>(lds + cur * kIB, a0, g0, acc, nx, lds + (cur ^ 1) * kIB, m, pre, mid);
+    rot_advance(rot, hb + LNERF_DW16_DEPTH, hb1);
+    auto mid = [&](int rounds) { issue_loads_at<a24k(PL)>(rot.pa, rot.pg, kt, nt, m, fr, rounds); };
+    const unsigned cur = rot.img;
+    rot.img = (kIB & (kIB - 1)) == 0 ? cur ^ kIB : kIB - cur;
+    block_mma<PL, TI, TJ, ACTIVE, FULL>(lds + cur, a0, g0, acc, nx, lds + rot.img, m, dbs, hb + 1 < hb1, pre, mid);
     __syncthreads();
 }
 
 template <int PL, int TI, int TJ, bool ACTIVE, bool FULL>
 __device__ __forceinline__ void hb_loop3(const float* A, const float* G, const float2* tab, int kt, int nt,
                                          const RowMap& m, int hb0, int hb1, int a0, int g0, fx16 (&acc)[TI][TJ],
-                                         Loads& L0, Loads& L1, Loads& L2, fx4 (&dbs)[kRPO], unsigned char* lds,
-                                         float2& scn) {
+                                         Loads& L0, Loads& L1, Loads& L2, DbSums& dbs, unsigned char* lds,
+                                         float2& scn, Rot& rot) {
     // whole triples only (one loop body; remainder copies make the compiler spill the
     // accumulators): the steps past hb1 split zero-scaled (zero) planes and add nothing
     for (int hb = hb0; hb < hb1; hb += 3) {
-        hb_step3<PL, TI, TJ, ACTIVE, FULL, 0>(A, G, tab, kt, nt, m, hb, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
-        hb_step3<PL, TI, TJ, ACTIVE, FULL, 1>(A, G, tab, kt, nt, m, hb + 1, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
-        hb_step3<PL, TI, TJ, ACTIVE, FULL, 2>(A, G, tab, kt, nt, m, hb + 2, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
+        hb_step3<PL, TI, TJ, ACTIVE, FULL, 0>(A, G, tab, kt, nt, m, hb, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, scn, rot);
+        hb_step3<PL, TI, TJ, ACTIVE, FULL, 1>(A, G, tab, kt, nt, m, hb + 1, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, scn, rot);
+        hb_step3<PL, TI, TJ, ACTIVE, FULL, 2>(A, G, tab, kt, nt, m, hb + 2, hb0, hb1, a0, g0, acc, L0, L1, L2, dbs, lds, scn, rot);
     }
 }
 
@@ -655,35 +726,34 @@ __device__ __forceinline__ void hb_loop3(const float* A, const float* G, const f
 template <int PL, int TI, int TJ, bool ACTIVE, bool FULL, int I>
 __device__ __forceinline__ void hb_step2(const float* A, const float* G, const float2* tab, int kt, int nt,
                                          const RowMap& m, int hb, int hb0, int hb1, int a0, int g0,
-                                         fx16 (&acc)[TI][TJ], Loads& L0, Loads& L1, fx4 (&dbs)[kRPO],
-                                         unsigned char* lds, float2& scn) {
+                                         fx16 (&acc)[TI][TJ], Loads& L0, Loads& L1, DbSums& dbs,
+                                         unsigned char* lds, float2& scn, Rot& rot) {
     constexpr int kIB = image_bytes<PL>();
     Loads& fr = I == 0 ? L0 : L1;
     const Loads& nx = I == 0 ? L1 : L0;
     auto pre = [&]() {
-        if (hb + 1 < hb1) {
-#pragma unroll
-            for (int i = 0; i < kRPO; ++i) dbs[i] += nx.v[kRPO + i];
-        }
         // (hb + 1's entry was fetched a step ahead, so nothing here waits for the table; hb + 2's follows)
         const SampleScale sc = decode_scale(scn);
         scn = tab[(hb + 2 - hb0) * 16];
         return sc;
     };
     // (round_by_round above)
-    auto mid = [&](int rounds) { issue_loads<a24k(PL)>(A, G, kt, nt, m, hb + LNERF_DW16_DEPTH, hb1, fr, rounds); };
-    const int cur = (hb - hb0) & 1;
-    block_mma<PL, TI, TJ, ACTIVE, FULL>(lds + cur * kIB, a0, g0, acc, nx, lds + (cur ^ 1) * kIB, m, pre, mid);
+    rot_advance(rot, hb + LNERF_DW16_DEPTH, hb1);
+    auto mid = [&](int rounds) { issue_loads_at<a24k(PL)>(rot.pa, rot.pg, kt, nt, m, fr, rounds); };
+    const unsigned cur = rot.img;
+    rot.img = (kIB & (kIB - 1)) == 0 ? cur ^ kIB : kIB - cur;
+    block_mma<PL, TI, TJ, ACTIVE, FULL>(lds + cur, a0, g0, acc, nx, lds + rot.img, m, dbs, hb + 1 < hb1, pre, mid);
     __syncthreads();
 }
 
 template <int PL, int TI, int TJ, bool ACTIVE, bool FULL>
 __device__ __forceinline__ void hb_loop2(const float* A, const float* G, const float2* tab, int kt, int nt,
                                          const RowMap& m, int hb0, int hb1, int a0, int g0, fx16 (&acc)[TI][TJ],
-                                         Loads& L0, Loads& L1, fx4 (&dbs)[kRPO], unsigned char* lds, float2& scn) {
+                                         Loads& L0, Loads& L1, DbSums& dbs, unsigned char* lds, float2& scn,
+                                         Rot& rot) {
     for (int hb = hb0; hb < hb1; hb += 2) {
-        hb_step2<PL, TI, TJ, ACTIVE, FULL, 0>(A, G, tab, kt, nt, m, hb, hb0, hb1, a0, g0, acc, L0, L1, dbs, lds, scn);
-        hb_step2<PL, TI, TJ, ACTIVE, FULL, 1>(A, G, tab, kt, nt, m, hb + 1, hb0, hb1, a0, g0, acc, L0, L1, dbs, lds, scn);
+        hb_step2<PL, TI, TJ, ACTIVE, FULL, 0>(A, G, tab, kt, nt, m, hb, hb0, hb1, a0, g0, acc, L0, L1, dbs, lds, scn, rot);
+        hb_step2<PL, TI, TJ, ACTIVE, FULL, 1>(A, G, tab, kt, nt, m, hb + 1, hb0, hb1, a0, g0, acc, L0, L1, dbs, lds, scn, rot);
     }
 }
 
@@ -875,9 +945,11 @@ __device__ __forceinline__ void dw_split(const Dw16Args& a, int l, int sp, unsig
 #pragma unroll
         for (int j = 0; j < TJ; ++j) acc[i][j] = fx16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // db: this thread's G values are features image_row(i) - 256 ..+3 of one sample, i = 2, 3
-    fx4 dbs[kRPO];
+    DbSums dbs;
 #pragma unroll
-    for (int i = 0; i < kRPO; ++i) dbs[i] = fx4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int i = 0; i < kRPO; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dbs[i][j] = 0.0f;
 
     const float* A = a.act + a.a_off[l];
     const float* G = a.grad + a.g_off[l];
@@ -898,31 +970,36 @@ __device__ __forceinline__ void dw_split(const Dw16Args& a, int l, int sp, unsig
         xany |= fill_scales<PL>(tab, se, E, c0, c1);
         const float2* tabt = tab + m.isamp;
 #if LNERF_DW16_DEPTH == 2
+        Rot rot = rot_begin<a24k(PL)>(A, G, KT, NT, c0);
         Loads L0, L1;
-        issue_loads<a24k(PL)>(A, G, KT, NT, m, c0, c1, L0);
-        issue_loads<a24k(PL)>(A, G, KT, NT, m, c0 + 1, c1, L1);
+        issue_loads_at<a24k(PL)>(rot.pa, rot.pg, KT, NT, m, L0, kAllRounds);
+        rot_advance(rot, c0 + 1, c1);
+        issue_loads_at<a24k(PL)>(rot.pa, rot.pg, KT, NT, m, L1, kAllRounds);
 #else
+        Rot rot = rot_begin<a24k(PL)>(A, G, KT, NT, c0);
         Loads L0, L1, L2;
-        issue_loads<a24k(PL)>(A, G, KT, NT, m, c0, c1, L0);
-        issue_loads<a24k(PL)>(A, G, KT, NT, m, c0 + 1, c1, L1);
-        issue_loads<a24k(PL)>(A, G, KT, NT, m, c0 + 2, c1, L2);
+        issue_loads_at<a24k(PL)>(rot.pa, rot.pg, KT, NT, m, L0, kAllRounds);
+        rot_advance(rot, c0 + 1, c1);
+        issue_loads_at<a24k(PL)>(rot.pa, rot.pg, KT, NT, m, L1, kAllRounds);
+        rot_advance(rot, c0 + 2, c1);
+        issue_loads_at<a24k(PL)>(rot.pa, rot.pg, KT, NT, m, L2, kAllRounds);
 #endif
         __syncthreads();   // the table is written
 #pragma unroll
-        for (int i = 0; i < kRPO; ++i) dbs[i] += L0.v[kRPO + i];
+        for (int i = 0; i < kRPO; ++i) db_add(dbs, L0, i, true);
         write_planes<PL>(L0, lds, decode_scale(tabt[0]), m);
         float2 scn = tabt[16];   // the scales of c0 + 1, a step ahead (hb_step3)
         __syncthreads();
 #if LNERF_DW16_DEPTH == 2
-        if (active && full) hb_loop2<PL, TI, TJ, true, true>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, dbs, lds, scn);
-        else if (active) hb_loop2<PL, TI, TJ, true, false>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, dbs, lds, scn);
-        else if (full) hb_loop2<PL, TI, TJ, false, true>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, dbs, lds, scn);
-        else hb_loop2<PL, TI, TJ, false, false>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, dbs, lds, scn);
+        if (active && full) hb_loop2<PL, TI, TJ, true, true>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, dbs, lds, scn, rot);
+        else if (active) hb_loop2<PL, TI, TJ, true, false>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, dbs, lds, scn, rot);
+        else if (full) hb_loop2<PL, TI, TJ, false, true>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, dbs, lds, scn, rot);
+        else hb_loop2<PL, TI, TJ, false, false>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, dbs, lds, scn, rot);
 #else
-        if (active && full) hb_loop3<PL, TI, TJ, true, true>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
-        else if (active) hb_loop3<PL, TI, TJ, true, false>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
-        else if (full) hb_loop3<PL, TI, TJ, false, true>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
-        else hb_loop3<PL, TI, TJ, false, false>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, L2, dbs, lds, scn);
+        if (active && full) hb_loop3<PL, TI, TJ, true, true>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, L2, dbs, lds, scn, rot);
+        else if (active) hb_loop3<PL, TI, TJ, true, false>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, L2, dbs, lds, scn, rot);
+        else if (full) hb_loop3<PL, TI, TJ, false, true>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, L2, dbs, lds, scn, rot);
+        else hb_loop3<PL, TI, TJ, false, false>(A, G, tabt, KT, NT, m, c0, c1, a0, g0, acc, L0, L1, L2, dbs, lds, scn, rot);
 #endif
     }
 
